@@ -8,6 +8,11 @@ One step = one `render_rays` call over this rank's rays (BASELINE.json configs[1
 and, for N > 1, its RCCL all-reduce.  Rays are sharded by rank with no data-path collective ("weak" scaling:
 every GPU renders its own 65536 rays, as every DDP rank of the reference renders its own lines).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, settles, warms up, times exactly --steps steps and prints the line.  --full adds the secondary
+figures to the same line: the other precision modes on the same batch, the other BASELINE configurations, the one-GPU
+strong-scaling prediction, the weak-scaling leg of an N > 1 run and the CPU baseline.  --dump-outputs DIR writes what
+the last timed step returned (rank 0) as DIR/<name>.npy, float32 or float64, at most 64 MB in all.
 """
 import argparse
 import json
@@ -33,6 +38,46 @@ FLOP_PER_SAMPLE = 2 * (COARSE_MACS + 2 * SKIN_MACS)   # 1,394,560
 PEAK_BF16_TFLOPS = 2500.0                              # dense bf16 MFMA, MI355X_MICROARCH.md
 PEAK_F32_TFLOPS = 157.3
 PARITY_GRADE = ("fp16", "bf16x3", "fp32")              # render modes held to the north star's 1e-4 bar against the fp32 oracle
+DUMP_LIMIT_BYTES = 64_000_000                          # --dump-outputs: bytes written in all (files included)
+
+
+def dump_outputs(path, arrays, rows=None, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor of `arrays` as <path>/<name>.npy (float64 stays float64, everything else float32).  When
+    the whole set exceeds `limit`, the per-ray arrays (leading dimension `rows`) are kept whole from the narrowest up to a
+    quarter of the limit, and the wider ones share ONE fixed sample of rows (seed 0, sorted) sized to fill the rest, so that
+    the same arguments always give the same files.  <path>/manifest.json records each array's full shape and the sample."""
+    arrays = {k: v.detach() for k, v in arrays.items() if torch.is_tensor(v)}
+    size = lambda t: t.numel() * (8 if t.dtype == torch.float64 else 4)
+    per_ray = sorted((k for k, v in arrays.items() if rows and v.dim() > 0 and v.shape[0] == rows),
+                     key=lambda k: (size(arrays[k]), k))
+    fixed = sum(size(v) for k, v in arrays.items() if k not in per_ray)
+    room = limit - (1 << 16)                                 # .npy headers and manifest.json
+    sampled, idx = [], None
+    if fixed + sum(size(arrays[k]) for k in per_ray) > room:
+        whole = fixed
+        for i, k in enumerate(per_ray):
+            if whole + size(arrays[k]) > room // 4:
+                sampled = per_ray[i:]
+                break
+            whole += size(arrays[k])
+        per_row = sum(size(arrays[k]) for k in sampled) // rows if sampled else 0
+        n_keep = (room - whole) // per_row if per_row else 0
+        if n_keep < 1:
+            raise ValueError(f"--dump-outputs: {whole} bytes of whole arrays leave no room under {limit}")
+        idx = np.sort(np.random.default_rng(0).permutation(rows)[:n_keep])
+    os.makedirs(path, exist_ok=True)
+    manifest = {"limit_bytes": limit, "sample": None if idx is None else {
+        "rows": rows, "kept": int(idx.size), "seed": 0, "how": "np.sort(np.random.default_rng(0).permutation(rows)[:kept])",
+        "arrays": sampled}, "arrays": {}}
+    for k, v in arrays.items():
+        a = v.double() if v.dtype == torch.float64 else v.float()
+        if k in sampled:
+            a = a[torch.from_numpy(idx).to(a.device)]
+        a = a.cpu().numpy()
+        np.save(os.path.join(path, k + ".npy"), a)
+        manifest["arrays"][k] = {"shape": list(v.shape), "stored_shape": list(a.shape), "dtype": str(a.dtype)}
+    with open(os.path.join(path, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
 
 
 def physical_cores():
@@ -206,6 +251,15 @@ def train_mode(args, world, rank, local, dist):
         h.step()
     fence()
     dt = sharding.max_over_ranks(time.perf_counter() - t0, dev, dist, world)
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step leaves a caller: the loss sums it returns, its weighted loss terms, the updated parameters
+        outs = {"loss_sums": h.loss_buf, "loss_terms": h.terms}
+        for mk, m in h.models.items():
+            if isinstance(m, torch.nn.Module):
+                outs.update({f"param.{mk}.{n}": p for n, p in m.named_parameters()})
+            elif isinstance(m, torch.nn.Parameter):
+                outs[f"param.{mk}"] = m
+        dump_outputs(args.dump_outputs, outs)
     # DDP contract: every rank has applied the same averaged gradients, so the ranks' parameters are identical
     per_rank = sharding.gather_counts(h.N, dev, dist, world)
     chk = torch.stack([p.detach().double().sum() for p in h.params]).sum().reshape(1)
@@ -465,8 +519,15 @@ def main():
     ap.add_argument("--settle-steps", type=int, default=60, help="train mode: untimed eager steps before the graph capture "
                     "(a fixed count, so that the printed loss is a deterministic function of the build)")
     ap.add_argument("--lr", type=float, default=5e-4, help="train mode: AdamW learning rate (reference default, moda.py:90)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32", action="store_true", help="skip the secondary exact-fp32 figure (profiling runs: only the timed workload's kernels)")
+    ap.add_argument("--full", action="store_true",
+                    help="render mode: add the secondary figures to the line (other precision modes on the same batch, cfg3 / "
+                         "cfg4 / cfg5, the strong-scaling prediction, the weak leg of an N > 1 run, the CPU baseline); a plain "
+                         "run times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy: float32 / float64, "
+                         "at most 64 MB in all (a fixed, seeded sample of the rays of the larger arrays; DIR/manifest.json)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fp32", action="store_true", help="with --full: skip the secondary precision-mode figures (profiling runs: only the timed workload's kernels)")
     ap.add_argument("--no-graph", action="store_true", help="train mode: time the eagerly launched step instead of the HIP graph")
     ap.add_argument("--layout", default="rays", choices=["rays", "frames"],
                     help="render mode: 'rays' = the reference's layout (per-frame tensors repeated per ray, moda.py:1281-1311); "
@@ -475,14 +536,16 @@ def main():
                     help="render mode, N > 1: strong = ONE batch of --rays rays cut into contiguous per-rank ranges "
                          "(sharding.shard_rays; the north star's 'shard rays across the 8 GPUs'); weak = every GPU renders its own "
                          "--rays rays (each DDP rank of the reference renders its own lines); both (default) = `value` is the "
-                         "strong figure and the line also carries `weak_rays_per_s`")
-    ap.add_argument("--no-configs", action="store_true", help="skip the secondary figures (cfg3 / cfg4 / cfg5, bf16-vs-fp32 error, "
+                         "strong figure and, with --full, the line also carries `weak_rays_per_s`")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the secondary figures (cfg3 / cfg4 / cfg5, "
                     "strong-scaling prediction): profiling runs")
     ap.add_argument("--mode", default="render", choices=["render", "train"],
                     help="render: the headline metric (forward render_rays, BASELINE configs[1]); "
                          "train: one full training step per rank (configs[3] shape: 2048 rays x 128 samples, "
                          "forward + backward + AdamW, gradients and loss all-reduced over RCCL)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.precision is None:
         args.precision = "bf16" if args.mode == "train" else "fp16"
@@ -535,7 +598,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def leg(strong, steps, settle):
+    def leg(strong, steps, settle, dump=False):
         """One timed leg.  strong: ONE batch of N rays, every rank builds it and keeps its contiguous range (sharding.shard_rays:
         the north star's "shard rays across the 8 GPUs"); weak: every rank owns its own N rays (each DDP rank of the reference
         renders its own lines).  W warm-up steps, then exactly `steps` steps between barrier + synchronize brackets, max over ranks."""
@@ -555,9 +618,12 @@ def main():
         target = target.to(bench_support.DEV)
         n_local = rays["rays_d"].shape[0]
         loss_buf = torch.zeros(2, device=bench_support.DEV)
+        last = {}
 
-        def step(collective=True):
+        def step(collective=True, keep=False):
             res = moda_amd.render_rays(models, emb, rays, N_samples=S, perturb=0, noise_std=0.0, opts=opts, img_size=512)
+            if keep:                                                 # --dump-outputs: the last timed step's result
+                last.update(res)
             sharding.photometric_sums(res["img_coarse"], target, out=loss_buf)
             if not collective:
                 return loss_buf
@@ -577,23 +643,29 @@ def main():
             fence()
             _lib.PROFILE = {}
             t0 = time.perf_counter()
-            for _ in range(steps):
-                lb = step()
+            for i in range(steps):
+                lb = step(keep=dump and i == steps - 1)
             fence()
             dt = time.perf_counter() - t0
             prof, _lib.PROFILE = _lib.PROFILE, None
         per_rank = sharding.gather_counts(n_local, bench_support.DEV, dist, world)
+        if dump:
+            last["loss_sums"] = lb
         return {"rays": rays, "target": target, "n_local": n_local, "n_job": N if strong else N * world, "n_settle": n_settle,
                 "dt": sharding.max_over_ranks(dt, bench_support.DEV, dist, world), "loss": sharding.mean_loss(lb), "prof": prof,
-                "per_rank": per_rank, "steps": steps}
+                "per_rank": per_rank, "steps": steps, "outputs": last}
 
     # N = 1: one leg (strong and weak coincide).  N > 1: `value` is the STRONG figure -- one batch of --rays rays cut across the
     # ranks, the north star's sharding -- and the same line carries the weak figure (every rank its own --rays rays) beside it,
     # timed over a third of the steps.  --scaling weak|strong restricts the run to one leg (`value` is then that leg's).
     strong = args.scaling in ("both", "strong") or world == 1
-    main_leg = leg(strong, args.steps, args.settle)
+    main_leg = leg(strong, args.steps, args.settle, dump=bool(args.dump_outputs) and rank == 0)
+    if rank == 0 and args.dump_outputs:
+        # this rank's rays (with N > 1: its shard) as render_rays returned them, and the loss sums the step returns
+        dump_outputs(args.dump_outputs, main_leg.pop("outputs"), rows=main_leg["n_local"])
+    main_leg.pop("outputs", None)
     weak_leg = None
-    if world > 1 and args.scaling == "both":
+    if args.full and world > 1 and args.scaling == "both":
         weak_leg = leg(False, max(args.steps // 3, 3), 0.0)
     rays, target, n_local, n_job, n_settle = (main_leg[k] for k in ("rays", "target", "n_local", "n_job", "n_settle"))
     dt, loss, prof = main_leg["dt"], main_leg["loss"], main_leg["prof"]
@@ -661,7 +733,7 @@ def main():
     # (N = 1 only: with several ranks these legs would keep rank 0 busy for ~15 s while the others sit in the process group's
     #  teardown, and they describe one GPU anyway)
     xb = None
-    if rank == 0 and world == 1 and args.precision in ("bf16", "fp16") and not args.no_fp32 and n_sub > 0:
+    if args.full and rank == 0 and world == 1 and args.precision in ("bf16", "fp16") and not args.no_fp32 and n_sub > 0:
         keys = ("img_coarse", "depth_rnd", "sil_coarse", "xyz_canonical_vis", "frame_cyc_dis")
         moda_amd.set_precision("fp32")
         t_f, r_f = timed_render(models, emb, sub, 3, **render_kw)
@@ -699,7 +771,7 @@ def main():
     # strong-scaling prediction from ONE GPU: a rank of an 8-GPU strong-scaling job renders 1/8 of the batch; its time against
     # 1/8 of the full batch's time is the efficiency the fixed per-call costs (code folds, table kernels, small launches) allow
     strong_pred = None
-    if rank == 0 and world == 1 and not args.no_configs and n_local >= 8 * 256:
+    if args.full and rank == 0 and world == 1 and not args.no_configs and n_local >= 8 * 256:
         n8 = n_local // 8 // 256 * 256
         sub8 = {k: (v[:n8 // (256 if per_frame(v) else 1)] if torch.is_tensor(v) else v) for k, v in rays.items()}
         t_full = dt / args.steps
@@ -711,7 +783,7 @@ def main():
 
     # the other BASELINE configurations, so that the driver's record carries them
     configs = None
-    if rank == 0 and world == 1 and not args.no_configs and args.precision in ("bf16", "fp16"):
+    if args.full and rank == 0 and world == 1 and not args.no_configs and args.precision in ("bf16", "fp16"):
         configs = other_configs(args, timed_render)
 
     def gpu_cfg1_check(cpu_res):
@@ -783,7 +855,7 @@ def main():
                          "executed_tflops": 2 * COARSE_MACS_EXECUTED * units / (kern_ms * 1e-3) / 1e12 if units else float("nan"),
                          "executed_frac_of_peak": 2 * COARSE_MACS_EXECUTED * units / (kern_ms * 1e-3) / 1e12 / peak if units else float("nan")},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(B, gpu_check=gpu_cfg1_check)
         out["collective_backend"] = dist.get_backend() if sharding.live(world) else None
         print(json.dumps(out))

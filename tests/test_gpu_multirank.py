@@ -19,7 +19,7 @@ def _run(extra, n=2, settle="0"):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1", "--nnodes=1",
-           f"--nproc-per-node={n}", os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--no-cpu-baseline", "--no-fp32",
+           f"--nproc-per-node={n}", os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--full", "--no-cpu-baseline", "--no-fp32",
            "--no-configs", "--settle", settle] + extra
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]

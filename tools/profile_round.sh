@@ -4,8 +4,8 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 T=${1:-r06}
 O=gpurun_out/$T
 mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
-python bench.py --precision bf16 --no-configs > $O/bench_bf16.json 2>> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
+python bench.py --full --precision bf16 --no-configs > $O/bench_bf16.json 2>> $O/bench.err
 for P in bf16 bf16x6 fp32; do python bench.py --mode train --precision $P > $O/bench_train_$P.json 2>> $O/bench.err; done
 python bench.py --mode train --precision bf16 --rays 8192 --samples 256 --steps 30 --settle-steps 12 > $O/bench_train_bf16_cfg4_8192x256.json 2>> $O/bench.err
 python bench.py --mode train --precision bf16 --fine --unc --steps 30 --settle-steps 12 > $O/bench_train_bf16_cfg5_2048x128.json 2>> $O/bench.err
