@@ -451,6 +451,45 @@ int moda_sum_tensors(const float* const* xs, int32_t n, int64_t numel, float* ou
 int moda_affine3(const float* x, const float* y, const float* scale, float post, const float* shift, int64_t rows, float* out,
                  void* stream);
 
+/* ------------------------------------------------------------------------
+ * Mesh extraction after the lattice queries (moda_amd/csrc/mesh_kernels.hip; additive entries of ABI 9: no existing
+ * signature changed).  vol, vis (g0,g1,g2) fp32 C order, vis nullable; a corner is occupied iff its value is finite and
+ * > threshold, the value being -1 where vis < 0.5.  int32 indices: MODA_ESHAPE when any g < 2 or 3*g0*g1*g2 >= 2^31.
+ * The caller reads `totals` back before it sizes the outputs, so these refuse a capturing stream (MODA_EINVAL).
+ * Scan workspace: tile_sum int32 and tile_off int64, ceil(n / MODA_MC_SCAN_TILE) entries each for the largest n scanned.
+ * ------------------------------------------------------------------------ */
+#define MODA_MC_SCAN_TILE 2048
+
+/* moda_mc_count: the counting half of marching cubes (train_utils.py:1441 mcubes.marching_cubes, with the vis mask of :1425
+ * fused into the reads).  mask (g0*g1*g2 uint8): bit d = the +axis-d edge from the point crosses; cell_case ((g0-1)(g1-1)(g2-1)
+ * uint8): case index of each cell (bit c = corner (c&1, c>>1&1, c>>2&1) occupied); voff / foff: exclusive scans of the vertex
+ * and triangle counts (first vertex id per point, first face per cell); totals int64[3] = {vertices, faces, occupied corners}
+ * (the last is the numerator of the "fraction occupied" message, :1435).  The lattice limit does not bound the face total:
+ * cases of 4-5 triangles per cell can reach 2^31 faces on a lattice that passes it.  A faces total >= 2^31 means refusal
+ * (moda_mc_emit returns MODA_ESHAPE for it), and foff is not valid then. */
+int moda_mc_count(const float* vol, const float* vis, int64_t g0, int64_t g1, int64_t g2, float threshold, uint8_t* mask,
+                  uint8_t* cell_case, int32_t* voff, int32_t* foff, int32_t* tile_sum, int64_t* tile_off, int64_t* totals,
+                  void* stream);
+
+/* moda_mc_emit: vertices (n_vertices,3) fp32, one per crossing edge in C order of the edge's lower point then axis, at
+ * t = (thr - v_a) / (v_b - v_a) (the finite end when the other is not finite), mapped per axis by out = p * scale + shift
+ * (scale 1, shift 0: lattice-index coordinates as mcubes returns them; scale 2b/g, shift -b: the world mapping of
+ * train_utils.py:1442); faces (n_faces,3) int32 by cell in C order, then in table order.  n_vertices / n_faces: totals[0..1]
+ * of moda_mc_count on the same inputs. */
+int moda_mc_emit(const float* vol, const float* vis, int64_t g0, int64_t g1, int64_t g2, float threshold, const uint8_t* mask,
+                 const uint8_t* cell_case, const int32_t* voff, const int32_t* foff, double scale_x, double scale_y,
+                 double scale_z, double shift_x, double shift_y, double shift_z, int64_t n_vertices, int64_t n_faces,
+                 float* vertices, int32_t* faces, void* stream);
+
+/* moda_mesh_largest_part (train_utils.py:1447-1451, use_cc: trimesh split + keep the part with the most vertices): ties go to the
+ * part that holds the lowest vertex index.  Workspace parent, label, count, vnew (n_vertices int32 each), fnew (n_faces int32);
+ * vertices_out (n_vertices,3) / faces_out (n_faces,3) receive the kept part in its original order (faces remapped);
+ * totals int64[4] = {kept vertices, kept faces, internal, faces with an index outside [0, n_vertices)}: such faces are skipped
+ * (never read through) and the caller must treat a nonzero totals[3] as an error. */
+int moda_mesh_largest_part(const float* vertices, const int32_t* faces, int64_t n_vertices, int64_t n_faces, int32_t* parent,
+                           int32_t* label, int32_t* count, int32_t* vnew, int32_t* fnew, int32_t* tile_sum, int64_t* tile_off,
+                           int64_t* totals, float* vertices_out, int32_t* faces_out, void* stream);
+
 /* dz = dy * act'(y): act 1 relu, 2 sigmoid */
 int moda_act_bwd(const float* dy, const float* y, int64_t n, int32_t act, float* dz, void* stream);
 

@@ -14,6 +14,8 @@ from .loss_utils import (visibility_loss, compute_pts_exp, feat_match_loss, feat
 from .feeders import (raycast, sample_xy, chunk_rays, FrameCode, DQ_RTHead, correct_bones, correct_rest_pose,  # noqa: F401
                       update_rays, update_delta_rts)
 from .mesh_queries import warp_bw, warp_fw, query_volume  # noqa: F401
+from . import mesh  # noqa: F401
+from .mesh import TriMesh, marching_cubes, largest_part, extract_mesh  # noqa: F401
 from . import checkpoint  # noqa: F401
 from . import overflow  # noqa: F401
 from .autograd import set_train_precision, get_train_precision, GradBucket  # noqa: F401

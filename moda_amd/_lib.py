@@ -122,6 +122,10 @@ _SIGNATURES = {
     "moda_logsig_loss": (_c.c_int, [_P, _P, _I64, _F32, _F32, _P, _P, _P, _P]),
     "moda_sum_tensors": (_c.c_int, [_c.POINTER(_P), _I32, _I64, _P, _P]),
     "moda_affine3": (_c.c_int, [_P, _P, _P, _F32, _P, _I64, _P, _P]),
+    # mesh extraction (mesh_kernels.hip): additive entries of ABI 9
+    "moda_mc_count": (_c.c_int, [_P, _P, _I64, _I64, _I64, _F32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "moda_mc_emit": (_c.c_int, [_P, _P, _I64, _I64, _I64, _F32, _P, _P, _P, _P] + [_c.c_double] * 6 + [_I64, _I64, _P, _P, _P]),
+    "moda_mesh_largest_part": (_c.c_int, [_P, _P, _I64, _I64] + [_P] * 11),
 }
 
 EXPORTS = tuple(_SIGNATURES)
