@@ -490,6 +490,57 @@ int moda_mesh_largest_part(const float* vertices, const int32_t* faces, int64_t 
                            int32_t* label, int32_t* count, int32_t* vnew, int32_t* fnew, int32_t* tile_sum, int64_t* tile_off,
                            int64_t* totals, float* vertices_out, int32_t* faces_out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Point sets for mesh evaluation (moda_amd/csrc/pointset_kernels.hip; additive entries of ABI 9: no existing signature
+ * changed).  x (B,N,3), y (B,M,3) fp32 contiguous; int32 indices: MODA_ESHAPE when B < 1, M < 1, B*N >= 2^31 or
+ * B*M >= 2^31 (checked before any pointer).  None of these reads anything back: they may run on a capturing stream.
+ * ------------------------------------------------------------------------ */
+#define MODA_NN_QUERY_BLOCK 1024   /* queries per workgroup */
+#define MODA_NN_TILE 1024          /* targets per LDS tile; the ranges of a split are whole tiles */
+#define MODA_ICP_NSUM 17           /* doubles per batch element of moda_icp_moments */
+#define MODA_ICP_MAX_BLOCKS 256    /* partials: B * MODA_ICP_MAX_BLOCKS * MODA_ICP_NSUM doubles */
+
+/* moda_nn_fwd: nearest point of y for every point of x, brute force (third_party/chamfer3D/chamfer3D.cu:12-134
+ * NmDistanceKernel, one direction of it; pytorch3d knn_points with K = 1).  dist2 (B,N) fp32 =
+ * fma(dz, dz, fma(dy, dy, dx * dx)) with dx = x - y etc., each operation rounded once in fp32; idx (B,N) int32.  Among
+ * targets of equal computed distance the lowest index wins, however the work is split.  Every slot of dist2 and idx is
+ * written on every valid call; where no distance is finite and ordered (NaN or overflowing input) the slot holds +inf and
+ * index 0.  N == 0 returns 0 and does nothing.
+ * keys: workspace of B*N uint64, or NULL.  With it, and when B * ceil(N / MODA_NN_QUERY_BLOCK) workgroups would not fill the
+ * device, the targets are also split into moda_nn_splits() ranges whose results are combined as (bits(d) << 32) | idx under
+ * a 64-bit atomicMin -- order-free, so the output is bit-identical from run to run and to the unsplit result. */
+int moda_nn_fwd(const float* x, const float* y, int64_t B, int64_t N, int64_t M, float* dist2, int32_t* idx, uint64_t* keys,
+                void* stream);
+
+/* The number of target ranges moda_nn_fwd uses for this shape when it is given `keys` (1: keys is not touched and may be
+ * NULL); *range (nullable) receives the targets per range, a multiple of MODA_NN_TILE. */
+int32_t moda_nn_splits(int64_t B, int64_t N, int64_t M, int64_t* range);
+
+/* moda_chamfer_bwd: gradient of one direction of the Chamfer distance (chamfer3D.cu:155-174 NmDistanceGradKernel).  With
+ * g = 2 * grad_dist[i] and v = g * (x_i - y_idx[i]) (difference, then product, each rounded in fp32): grad_x[i] += v,
+ * grad_y[idx[i]] -= v.  Both ACCUMULATE (the caller zeroes them; two calls with the roles swapped give both directions);
+ * grad_y takes fp32 atomicAdd, so its sums depend on arrival order in the last bits.  A query whose idx is outside [0, M)
+ * is skipped and never read through. */
+int moda_chamfer_bwd(const float* x, const float* y, const int32_t* idx, const float* grad_dist, int64_t B, int64_t N, int64_t M,
+                     float* grad_x, float* grad_y, void* stream);
+
+/* moda_icp_moments: the sums one ICP step needs from a search result (pytorch3d.ops.iterative_closest_point as
+ * render_vis.py:390-392 calls it: corresponding_points_alignment's means and covariance, and the rmse of its stopping test).
+ * sums (B, MODA_ICP_NSUM) float64 per batch element, with yn_i = y[idx[i]]:
+ *   [0..2] sum x0   [3..5] sum yn   [6..14] sum x0 (x) yn, row-major (entry 6 + 3c + d = sum x0_c yn_d)   [15] sum |x0|^2
+ *   [16] sum |xt - yn|^2
+ * x0 NULL: entries 0-15 are not written; xt NULL: entry 16 is not written (one of them must be given).  Inputs are widened
+ * to float64 before any arithmetic.  Each workgroup reduces in a fixed tree and the partials are added in index order by a
+ * second kernel: no float atomics, bit-identical from run to run.  Queries whose idx is outside [0, M) are skipped.
+ * Also MODA_ESHAPE for N < 1. */
+int moda_icp_moments(const float* x0, const float* y, const int32_t* idx, const float* xt, int64_t B, int64_t N, int64_t M,
+                     double* partials, double* sums, void* stream);
+
+/* moda_sim3_apply: out = s * (x @ R) + T per batch element, row vectors (the update of pytorch3d's ICP loop, and
+ * render_vis.py:392).  rts (B,13) fp32 = R row-major (9), T (3), s (1).  A fixed FMA chain per coordinate, so the result of a
+ * batch element does not depend on B. */
+int moda_sim3_apply(const float* x, const float* rts, int64_t B, int64_t N, float* out, void* stream);
+
 /* dz = dy * act'(y): act 1 relu, 2 sigmoid */
 int moda_act_bwd(const float* dy, const float* y, int64_t n, int32_t act, float* dz, void* stream);
 

@@ -16,6 +16,9 @@ from .feeders import (raycast, sample_xy, chunk_rays, FrameCode, DQ_RTHead, corr
 from .mesh_queries import warp_bw, warp_fw, query_volume  # noqa: F401
 from . import mesh  # noqa: F401
 from .mesh import TriMesh, marching_cubes, largest_part, extract_mesh  # noqa: F401
+from . import mesh_eval  # noqa: F401
+from .mesh_eval import (nearest, chamfer_3DDist, fscore, iterative_closest_point, eval_mesh, ICPSolution,  # noqa: F401
+                        SimilarityTransform)
 from . import checkpoint  # noqa: F401
 from . import overflow  # noqa: F401
 from .autograd import set_train_precision, get_train_precision, GradBucket  # noqa: F401

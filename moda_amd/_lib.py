@@ -126,6 +126,12 @@ _SIGNATURES = {
     "moda_mc_count": (_c.c_int, [_P, _P, _I64, _I64, _I64, _F32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "moda_mc_emit": (_c.c_int, [_P, _P, _I64, _I64, _I64, _F32, _P, _P, _P, _P] + [_c.c_double] * 6 + [_I64, _I64, _P, _P, _P]),
     "moda_mesh_largest_part": (_c.c_int, [_P, _P, _I64, _I64] + [_P] * 11),
+    # point sets for mesh evaluation (pointset_kernels.hip): additive entries of ABI 9
+    "moda_nn_fwd": (_c.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "moda_nn_splits": (_I32, [_I64, _I64, _I64, _c.POINTER(_I64)]),
+    "moda_chamfer_bwd": (_c.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "moda_icp_moments": (_c.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "moda_sim3_apply": (_c.c_int, [_P, _P, _I64, _I64, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
