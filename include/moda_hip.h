@@ -541,6 +541,42 @@ int moda_icp_moments(const float* x0, const float* y, const int32_t* idx, const 
  * batch element does not depend on B. */
 int moda_sim3_apply(const float* x, const float* rts, int64_t B, int64_t N, float* out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Mesh rasteriser, forward only (moda_amd/csrc/raster_kernels.hip; additive entries of ABI 9: no existing signature changed).
+ * The reference's soft_rasterize kernel (third_party/softras/soft_renderer/cuda/soft_rasterize_cuda_kernel.cu:246-483) in the
+ * configuration of nnutils/moda.py:469-471: hard rgb aggregation, sigma_val 1e-12, prod alpha, vertex textures, both windings.
+ * int32 indices: MODA_ESHAPE when B, V, F or S < 1, S > 32768, B*S*S >= 2^31 or B*F >= 2^31 (checked before any pointer).
+ * The per-tile face lists live in LDS only, so there is no data-dependent buffer: nothing is read back, and both entries may
+ * run on a capturing stream (moda_amd.mesh_render.rasterize adds a finiteness check of its own that reads a flag back).
+ * ------------------------------------------------------------------------ */
+#define MODA_RASTER_TILE 16        /* pixels per tile side: one 256-lane workgroup per tile, one pixel per lane */
+#define MODA_RASTER_REC_DOUBLES 12 /* per (view, face) in `rec`: (A_k, B_k, C_k, z_k), k = 0..2, w_k = A_k x + B_k y + C_k */
+#define MODA_RASTER_BOX_INTS 4     /* per (view, face) in `box`: col0, row0, col1, row1 inclusive; col0 > col1 = empty face */
+
+/* moda_raster_fwd: verts (B,V,3) fp32 = (x, y) in NDC with y up and z the depth the near / far test and the 1/z weights see;
+ * faces (F,3) int32 shared by the views (faces_per_view = 0) or (B,F,3) (faces_per_view != 0).  Pixel (row, col) has its centre
+ * at x = (2 col + 1 - S) / S, y = (2 (S-1-row) + 1 - S) / S (:343-346).  A face covers a pixel when its barycentrics (:25-29,
+ * inverse edge matrix with the determinant clamped at +-1e-10, :274-286; formed in float64) all lie in [0, 1] (:47-50), either
+ * winding.
+ * zp = 1 / sum_k(w_clip_k / z_k) (:53-58, :423); a face with zp < near or zp > far does not colour the pixel (:424); the smallest
+ * zp wins, the lowest face index among equal zp (:429).  Outputs, (B,S,S): face_idx int32 (-1 = none), bary (B,S,S,3) = w_clip of
+ * the winner (0 where none), zbuf = its zp (0 where none), alpha = 1 where ANY face covers the pixel -- taken before the near /
+ * far test, as the reference's alpha is (:408-424) -- else 0.  Faces that index a vertex outside [0, V), faces whose float64
+ * determinant is exactly 0 and faces whose pixel box misses the image are skipped.
+ * rec: B*F*MODA_RASTER_REC_DOUBLES doubles and box: B*F*MODA_RASTER_BOX_INTS int32 of workspace, both 16-byte aligned.
+ * binned = 0: every face is sent to every tile (same arithmetic, same bits; the route the tiled one is tested against). */
+int moda_raster_fwd(const float* verts, const int32_t* faces, int32_t faces_per_view, int64_t B, int64_t V, int64_t F, int64_t S,
+                    float near, float far, int32_t binned, double* rec, int32_t* box, int32_t* face_idx, float* bary, float* zbuf,
+                    float* alpha, void* stream);
+
+/* moda_raster_interp: out (B,C,S,S) = sum_k bary_k * attrs[b, faces[face_idx][k], c] (forward_sample_texture for vertex
+ * textures, :190-191), background[c] (or 0 when background is NULL) where face_idx is not a face of [0, F).  attrs (B,V,C) fp32.
+ * One product and two FMAs per channel in a fixed order: the bits of a channel do not depend on C.  Also MODA_ESHAPE for C < 1
+ * or C > 65536. */
+int moda_raster_interp(const float* attrs, const int32_t* faces, int32_t faces_per_view, const int32_t* face_idx,
+                       const float* bary, const float* background, int64_t B, int64_t V, int64_t F, int64_t C, int64_t S,
+                       float* out, void* stream);
+
 /* dz = dy * act'(y): act 1 relu, 2 sigmoid */
 int moda_act_bwd(const float* dy, const float* y, int64_t n, int32_t act, float* dz, void* stream);
 

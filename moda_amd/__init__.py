@@ -19,6 +19,10 @@ from .mesh import TriMesh, marching_cubes, largest_part, extract_mesh  # noqa: F
 from . import mesh_eval  # noqa: F401
 from .mesh_eval import (nearest, chamfer_3DDist, fscore, iterative_closest_point, eval_mesh, ICPSolution,  # noqa: F401
                         SimilarityTransform)
+from . import mesh_render  # noqa: F401
+from . import soft_renderer  # noqa: F401
+from .mesh_render import rasterize, interpolate, render_dp, render_mesh  # noqa: F401
+from .geom_utils import obj_to_cam, pinhole_cam, render_color, render_flow, mask_aug  # noqa: F401
 from . import checkpoint  # noqa: F401
 from . import overflow  # noqa: F401
 from .autograd import set_train_precision, get_train_precision, GradBucket  # noqa: F401

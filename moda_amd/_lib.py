@@ -132,6 +132,9 @@ _SIGNATURES = {
     "moda_chamfer_bwd": (_c.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
     "moda_icp_moments": (_c.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
     "moda_sim3_apply": (_c.c_int, [_P, _P, _I64, _I64, _P, _P]),
+    # mesh rasteriser (raster_kernels.hip): additive entries of ABI 9
+    "moda_raster_fwd": (_c.c_int, [_P, _P, _I32, _I64, _I64, _I64, _I64, _F32, _F32, _I32] + [_P] * 7),
+    "moda_raster_interp": (_c.c_int, [_P, _P, _I32, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1,8 +1,10 @@
 """Skinning subset of the reference's nnutils/geom_utils.py (same names, argument meaning and tensor
 layouts), evaluated by the HIP library: evaluate_mlp :19-57, bone_transform :59-111 (neudbs branch),
 vec_to_sim3 :187-199, gauss_mlp_skinning :202-217, mlp_skinning :219-229, skinning :280-302,
-neu_dbs :372-456, dqs_blend_skinning :495-517.
+neu_dbs :372-456, dqs_blend_skinning :495-517; and the mesh-drawing helpers obj_to_cam :567-581, K2mat :596-652,
+pinhole_cam :654-673, render_color :675-694, render_flow :696-724, mask_aug :1369-1379 on the rasteriser of mesh_render.py.
 """
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -234,3 +236,99 @@ def warp(bones, dq, pts, dskin, skin_aux, backward, want_skin=False, cyc_ref=Non
     L.call("moda_warp_frames_fwd", L.ptr(b), per_set, L.ptr(q), k, 1 if backward else 0, L.ptr(p), L.ptr(pt), L.ptr(d),
            int(bool(dskin_bns)), L.ptr(aux), bs, N, B, L.ptr(out), L.ptr(skin), L.ptr(cr), L.ptr(cyc), L.ptr(ws), L.stream())
     return out, skin, cyc
+
+
+# ---- cameras and mesh drawing (plain torch around moda_amd.mesh_render) ----------------------------------------------------------
+def obj_to_cam(in_verts, Rmat, Tmat):
+    """geom_utils.py:567-581: verts (...,N,3), Rmat (...,3,3), Tmat (...,3) -> verts @ R^T + T."""
+    verts = in_verts.clone()
+    if verts.dim() == 2:
+        verts = verts[None]
+    verts = verts.view(-1, verts.shape[1], 3)
+    Rmat = Rmat.view(-1, 3, 3).permute(0, 2, 1)
+    Tmat = Tmat.view(-1, 1, 3)
+    verts = verts.matmul(Rmat) + Tmat
+    return verts.reshape(in_verts.shape)
+
+
+def K2mat(K):
+    """geom_utils.py:596-612: K (...,4) = fx, fy, px, py -> (bs,3,3)."""
+    K = K.view(-1, 4)
+    bs = K.shape[0]
+    Kmat = torch.zeros(bs, 3, 3, device=K.device)
+    Kmat[:, 0, 0] = K[:, 0]
+    Kmat[:, 1, 1] = K[:, 1]
+    Kmat[:, 0, 2] = K[:, 2]
+    Kmat[:, 1, 2] = K[:, 3]
+    Kmat[:, 2, 2] = 1
+    return Kmat
+
+
+def pinhole_cam(in_verts, K):
+    """geom_utils.py:654-673: verts (...,N,3), K (...,4) -> (x / (1e-6 + z), y / (1e-6 + z), z) after the intrinsics."""
+    verts = in_verts.clone()
+    verts = verts.view(-1, verts.shape[1], 3)
+    K = K.view(-1, 4)
+    Kmat = K2mat(K)
+    Kmat = Kmat.permute(0, 2, 1)
+    verts = verts.matmul(Kmat)
+    verts_z = verts[:, :, 2:3]
+    verts_xy = verts[:, :, :2] / (1e-6 + verts_z)
+    verts = torch.cat([verts_xy, verts_z], -1)
+    return verts.reshape(in_verts.shape)
+
+
+def render_color(renderer, in_verts, faces, colors, texture_type='vertex'):
+    """geom_utils.py:675-694: verts in NDC (...,N,3), faces (...,F,3), colors (...,N,C) -> (B, C + 1, S, S), the last channel
+    alpha.  The eye offset is subtracted here and once more by the renderer's look_at, as in the reference; y is pre-flipped.
+    C = 3 in the reference; any C here (render_dp draws all its channels in one call)."""
+    from . import soft_renderer as sr
+    if texture_type != 'vertex':
+        raise NotImplementedError("render_color: texture_type='surface' is not implemented (served: 'vertex')")
+    verts = in_verts.clone()
+    verts = verts.view(-1, verts.shape[-2], 3)
+    faces = faces.view(-1, faces.shape[-2], 3)
+    colors = colors.view(-1, colors.shape[-2], colors.shape[-1])
+    device = verts.device
+    offset = torch.Tensor(renderer.transform.transformer._eye).to(device)[np.newaxis, np.newaxis]
+    verts_pre = verts[:, :, :3] - offset
+    verts_pre[:, :, 1] = -1 * verts_pre[:, :, 1]
+    return renderer.render_mesh(sr.Mesh(verts_pre, faces, textures=colors, texture_type=texture_type))
+
+
+def render_flow(renderer, verts, faces, verts_n):
+    """geom_utils.py:696-724: the NDC position of every drawn surface point in the next frame minus the pixel's own, on the
+    reference's `i * 2 / (w - 1) - 1` grid -> (B, h, w, 3), zero off the silhouette and in the last channel."""
+    verts = verts.view(-1, verts.shape[1], 3)
+    verts_n = verts_n.view(-1, verts_n.shape[1], 3)
+    faces = faces.view(-1, faces.shape[1], 3)
+    device = verts.device
+    rendered_ndc_n = render_color(renderer, verts, faces, verts_n)
+    _, _, h, w = rendered_ndc_n.shape
+    rendered_sil = rendered_ndc_n[:, -1]
+    ndc = np.meshgrid(range(w), range(h))
+    ndc = torch.Tensor(np.asarray(ndc)).to(device)[None]
+    ndc[:, 0] = ndc[:, 0] * 2 / (w - 1) - 1
+    ndc[:, 1] = ndc[:, 1] * 2 / (h - 1) - 1
+    flow = rendered_ndc_n[:, :2] - ndc
+    flow = flow.permute(0, 2, 3, 1)
+    flow = torch.cat([flow, rendered_sil[..., None]], -1)
+    flow[rendered_sil < 1] = 0.
+    flow[..., -1] = 0.
+    return flow
+
+
+def mask_aug(rendered):
+    """geom_utils.py:1369-1379: with probability 1/2 a random box of a (C,h,w) image is overwritten by the channel means
+    (np.random, the reference's draws in its order); in place."""
+    lb = 0.1
+    ub = 0.3
+    _, h, w = rendered.shape
+    if np.random.binomial(1, 0.5):
+        sx = int(np.random.uniform(lb * w, ub * w))
+        sy = int(np.random.uniform(lb * h, ub * h))
+        cx = int(np.random.uniform(sx, w - sx))
+        cy = int(np.random.uniform(sy, h - sy))
+        feat_mean = rendered.mean(-1).mean(-1)[:, None, None]
+        rendered[:, cx - sx:cx + sx, cy - sy:cy + sy] = feat_mean
+    return rendered
