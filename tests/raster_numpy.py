@@ -141,6 +141,30 @@ def icosphere(subdivisions, radius=1.0):
     return np.asarray(v) * radius, np.asarray(f, np.int64)
 
 
+def views(v, seeds, shift=(0.0, 0.0, 3.0), scale=1.0):
+    """(len(seeds), V, 3) fp32: the vertices under the rotation of each seed, scaled, then shifted (depth 3 by default)."""
+    return np.stack([v @ rotation(s).T * scale + np.asarray(shift) for s in seeds]).astype(np.float32)
+
+
+def sphere_volume(n=32):
+    """The synthetic SDF of tests/test_gpu_marching_cubes.py (`sphere`: off-lattice centre, radius 0.35 n), restated."""
+    ax = [np.arange(n, dtype=np.float64) - (n - 1) / 2 + o for o in (0.137, 0.071, -0.053)]
+    X, Y, Z = np.meshgrid(*ax, indexing="ij")
+    return (0.35 * n - np.sqrt(X ** 2 + Y ** 2 + Z ** 2)).astype(np.float32)
+
+
+def replicas(f):
+    """Face lists that hold every face of f (F,3) more than once, as (name, faces, index of the lowest copy of face i).
+    Copies have identical records, so they tie in depth at every pixel and the lowest copy must win: the image is the one of
+    f alone with face i renamed.  Where the copies sit decides which ordering they test: `tile` puts them F apart (other
+    256-face chunks, other flushes of the waiting list), `mirror` puts face i and its copy 2F-1-i into one chunk around the
+    middle of the list (another wave of the same chunk), `repeat` puts them side by side (neighbouring lanes of one wave)."""
+    F = len(f)
+    return [("tile", np.tile(f, (3, 1)), np.arange(F)),
+            ("mirror", np.concatenate([f, f[::-1]]), np.arange(F)),
+            ("repeat", np.repeat(f, 2, axis=0), 2 * np.arange(F))]
+
+
 def rotation(seed):
     """A rotation matrix drawn from the seed (QR of a Gaussian matrix, determinant +1)."""
     q, r = np.linalg.qr(np.random.default_rng(seed).standard_normal((3, 3)))

@@ -77,6 +77,34 @@ def test_matches_oracle(shape, kind, with_vis):
             assert err <= lattice_bound(shape), err
 
 
+@pytest.mark.parametrize("shape", [(17, 17, 17), (64, 64, 64)])
+@pytest.mark.parametrize("with_vis", [False, True])
+@pytest.mark.parametrize("thr", [0.0, 1.0])
+def test_integer_volume_exact_ties(shape, with_vis, thr):
+    """Values in {-2, .., 2}: a fifth of the corners that `vis` leaves EQUAL the threshold.  Occupancy is the strict >, so such a corner is empty
+    and a crossing edge that ends on it has t exactly 0 or 1: its vertex sits on the lattice point, where up to six edges
+    put one each, and triangles between them have no area.  Faces are the oracle's exactly; vertices within lattice_bound."""
+    vol = np.random.default_rng(21).integers(-2, 3, shape).astype(np.float32)
+    vis = np.random.default_rng(11).random(shape).astype(np.float32) * 0.6 + 0.1 if with_vis else None
+    rv, rf, _ = mcn.marching_cubes(vol, thr, vis)
+    # conditions on the input, on the oracle alone
+    assert (mcn.values(vol, vis) == thr).mean() > 0.05
+    on_lattice = (rv == np.round(rv)).all(1)
+    assert on_lattice.mean() > 0.05 and not on_lattice.all()
+    assert len(np.unique(rv, axis=0)) < len(rv)                                 # coincident vertices
+    tri = rv[rf]
+    flat = (np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]) == 0).all(1)
+    assert flat.any() and not flat.all()                                        # triangles without area
+    v, f = gpu_mc(vol, thr, vis)
+    assert f.shape == rf.shape and np.array_equal(f, rf), (shape, with_vis, thr)
+    assert v.shape == rv.shape
+    err = np.abs(v - rv).max()
+    print(shape, with_vis, thr, "V", len(v), "F", len(f), "on lattice", int(on_lattice.sum()), "flat", int(flat.sum()),
+          "max |dv|", err, "bound", lattice_bound(shape))
+    assert err <= lattice_bound(shape), err
+    assert np.array_equal(v[on_lattice], rv[on_lattice])                        # t = 0 and t = 1 are exact in any precision
+
+
 def test_world_affine_matches_oracle():
     shape, b = (33, 33, 33), np.asarray([0.31, 0.27, 0.45])
     vol = sphere(shape)

@@ -26,6 +26,7 @@ import torch
 
 import raster_numpy as rn
 from helpers import golden
+from test_raster_oracle import REPLICA_SCENES, REPLICA_SIZES, CHUNK_FACES, CHUNK_SEEDS, replica_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -42,8 +43,7 @@ def I(x):
     return torch.as_tensor(np.asarray(x), dtype=torch.int32, device=DEV)
 
 
-def views(v, seeds, shift=(0.0, 0.0, 3.0), scale=1.0):
-    return np.stack([v @ rn.rotation(s).T * scale + np.asarray(shift) for s in seeds]).astype(np.float32)
+views = rn.views
 
 
 def check_against_oracle(verts, faces, S, name, near=1.0, far=100.0, attrs=None):
@@ -114,16 +114,16 @@ def test_interpenetrating_spheres_and_off_screen():
     assert (al[2] == 0).all() and (al[3] > 0).any()
 
 
-def test_marching_cubes_mesh_matches_oracle():
-    # the synthetic SDF of tests/test_gpu_marching_cubes.py (`sphere`: off-lattice centre, radius 0.35 n), restated
-    n = 32
-    ax = [np.arange(n, dtype=np.float64) - (n - 1) / 2 + o for o in (0.137, 0.071, -0.053)]
-    X, Y, Z = np.meshgrid(*ax, indexing="ij")
-    vol = (0.35 * n - np.sqrt(X ** 2 + Y ** 2 + Z ** 2)).astype(np.float32)
-    v, f = M.marching_cubes(T(vol), 0.0)
+def mc_scene(n=32):
+    """The GPU marching-cubes mesh of the synthetic sphere SDF, scaled into the view volume."""
+    v, f = M.marching_cubes(T(rn.sphere_volume(n)), 0.0)
     v, f = v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(np.int64)
     assert len(f) > 3000
-    v = (v - (n - 1) / 2) / (0.5 * n) * 0.8
+    return (v - (n - 1) / 2) / (0.5 * n) * 0.8, f
+
+
+def test_marching_cubes_mesh_matches_oracle():
+    v, f = mc_scene()
     check_against_oracle(views(v, (12, 13)), f, 256, "marching cubes")
 
 
@@ -181,6 +181,81 @@ def test_binned_equals_unbinned_and_runs_are_identical():
     c = R.rasterize(T(vs), I(f), 257, binned=False)
     for x, y, z in zip(a, b, c):
         assert torch.equal(x, y) and torch.equal(x, z)
+
+
+# ---- the order guarantee: the lowest face index wins equal depths, wherever the equal faces sit in the list ----------------------
+# tests/test_raster_oracle.py holds the oracle to the same statements on the same face lists (REPLICA_SCENES, CHUNK_FACES).
+
+def _scene(name):
+    return mc_scene() if name == "marching cubes" else replica_scene(name)
+
+
+def _assert_replica(single, got, lowest, what):
+    """got = the render of a list in which face i of the single list first appears at index lowest[i]."""
+    fi, bw, zb, al = single
+    want = torch.where(fi >= 0, torch.as_tensor(lowest, dtype=torch.int32, device=DEV)[fi.clamp(min=0).long()], fi)
+    assert torch.equal(got[0], want), what + ": face_idx"
+    for x, y, k in zip(single[1:], got[1:], ("bary", "zbuf", "alpha")):
+        assert x.dtype == torch.float32 and torch.equal(x.view(torch.int32), y.view(torch.int32)), f"{what}: {k}"
+
+
+@pytest.mark.parametrize("binned", [True, False])
+@pytest.mark.parametrize("S", REPLICA_SIZES)
+@pytest.mark.parametrize("name", sorted(REPLICA_SCENES) + ["marching cubes"])
+def test_replicated_faces_keep_the_lowest_copy(name, S, binned):
+    """Copies of a face have identical records, hence identical zp in every lane; < is strict, so the lowest copy wins and
+    every other comparison is the one of the single list: all four outputs are the single render's bit for bit."""
+    v, f = _scene(name)
+    seeds = REPLICA_SCENES.get(name, (12, 13))
+    vs = T(views(v, seeds))
+    single = R.rasterize(vs, I(f), S, binned=binned)
+    covered = int((single[0] >= 0).sum())
+    assert covered > 0.2 * len(seeds) * S * S and len(torch.unique(single[0])) > 30
+    for kind, faces, lowest in rn.replicas(f):
+        got = R.rasterize(vs, I(faces), S, binned=binned)
+        _assert_replica(single, got, lowest, f"{name} S {S} binned {binned} {kind}")
+    print(f"{name} S {S} binned {binned}: F {len(f)}, {covered} pixels drawn, each a tie in every replica")
+
+
+def test_replicated_faces_match_the_oracle_and_per_view_lists():
+    S = 64
+    for name in sorted(REPLICA_SCENES):
+        v, f = replica_scene(name)
+        vs = views(v, REPLICA_SCENES[name][:2])
+        for kind, faces, lowest in rn.replicas(f):
+            fi = R.rasterize(T(vs), I(faces), S)[0].cpu().numpy()
+            for b in range(len(vs)):
+                # depth_margin is 0 wherever a copy ties: the face index is compared directly, at the pixels that the
+                # single list's margins clear
+                r1, r = rn.rasterize(vs[b][f], S), rn.rasterize(vs[b][faces], S)
+                ok = (r1.edge_margin > EDGE) & (r1.depth_margin > DEPTH)
+                assert (r1.alpha & ~ok).sum() <= CAP * r1.alpha.sum()
+                assert np.array_equal(fi[b][ok], r.face_idx[ok]), (name, kind, b)
+    # another face order per view, and the replicas of each view's own list
+    v, f = replica_scene("icosphere4")
+    vs = T(views(v, (31, 32, 33)))
+    rng = np.random.default_rng(1)
+    fpv = np.stack([f[rng.permutation(len(f))] for _ in range(3)])
+    single = R.rasterize(vs, I(fpv), 257)
+    assert int((single[0] >= 0).sum()) > 0.2 * 3 * 257 * 257
+    for kind in range(3):
+        per_view = [rn.replicas(x)[kind] for x in fpv]
+        assert all(np.array_equal(p[2], per_view[0][2]) for p in per_view)
+        got = R.rasterize(vs, I(np.stack([p[1] for p in per_view])), 257)
+        _assert_replica(single, got, per_view[0][2], f"per-view faces {per_view[0][0]}")
+
+
+@pytest.mark.parametrize("F", CHUNK_FACES)
+def test_face_counts_around_the_chunk_size(F):
+    """The first F faces of icosphere 4's list: the last 256-face chunk holds 255, 256, 1, .. faces."""
+    v, f = rn.icosphere(4, 0.9)
+    attrs = np.random.default_rng(F).uniform(-1, 1, (len(CHUNK_SEEDS), len(v), 3)).astype(np.float32)
+    fi = check_against_oracle(views(v, CHUNK_SEEDS), f[:F], 64, f"icosphere4[:{F}]", attrs=attrs)
+    assert (fi >= 0).any() and fi.max() < F
+    a = R.rasterize(T(views(v, CHUNK_SEEDS)), I(f[:F]), 64)
+    c = R.rasterize(T(views(v, CHUNK_SEEDS)), I(f[:F]), 64, binned=False)
+    for x, z in zip(a, c):
+        assert torch.equal(x, z)
 
 
 def rodrigues(a):

@@ -112,6 +112,60 @@ def test_zero_area_face_draws_nothing():
         assert np.isfinite(r.bary).all() and np.isfinite(r.zbuf).all()
 
 
+# ---- the scenes of the GPU order tests (tests/test_gpu_mesh_render.py imports these), held here on the oracle alone ----------
+REPLICA_SCENES = {"icosphere4": (41, 42, 43), "icosphere2": (44, 45)}         # name -> view seeds; F = 5120 and 320
+REPLICA_SIZES = (64, 257)
+CHUNK_FACES = (255, 256, 257, 511, 512, 513, 769)                             # around multiples of the kernel's 256-face chunk
+CHUNK_SEEDS = (50, 56)                                                        # views in which the last face of each list is drawn
+
+
+def replica_scene(name):
+    return rn.icosphere(int(name[-1]), 0.9)
+
+
+def _mc_scene(n=32):
+    """The marching-cubes scene of tests/test_gpu_mesh_render.py, from the numpy marching cubes."""
+    import mc_numpy as mcn
+    v, f, _ = mcn.marching_cubes(rn.sphere_volume(n), 0.0)
+    assert len(f) > 3000
+    return (v - (n - 1) / 2) / (0.5 * n) * 0.8, f
+
+
+def test_replicated_faces_keep_the_lowest_copy():
+    """A face list that holds every face several times draws the image of the single list, face i under the index of its lowest
+    copy, exactly: the copies tie at every pixel and only a strictly nearer face replaces the one that holds it."""
+    scenes = [(name, replica_scene(name), seeds[:1 if name == "icosphere4" else 2]) for name, seeds in sorted(REPLICA_SCENES.items())]
+    scenes.append(("marching cubes", _mc_scene(), (12,)))
+    for name, (v, f), seeds in scenes:
+        for S in REPLICA_SIZES:
+            for verts in rn.views(v, seeds):
+                one = rn.rasterize(verts[f], S)
+                drawn = one.face_idx >= 0
+                assert drawn.sum() > 0.2 * S * S
+                for kind, faces, lowest in rn.replicas(f):
+                    r = rn.rasterize(verts[faces], S)
+                    assert np.array_equal(r.face_idx, np.where(drawn, lowest[np.where(drawn, one.face_idx, 0)], -1)), (name, S, kind)
+                    assert np.array_equal(r.bary, one.bary) and np.array_equal(r.zbuf, one.zbuf) and np.array_equal(r.alpha, one.alpha)
+                    assert (r.depth_margin[drawn] == 0).all()                 # which is why check_against_oracle cannot be used on them
+
+
+def test_chunk_boundary_scenes_satisfy_the_left_out_cap():
+    """The condition tests/test_gpu_mesh_render.py puts on a scene (at most 1 % of the covered pixels inside the margins),
+    checked on the oracle alone for the first F faces of icosphere 4."""
+    v, f = rn.icosphere(4, 0.9)
+    for F in CHUNK_FACES:
+        last_drawn = 0
+        for b, verts in enumerate(rn.views(v, CHUNK_SEEDS)):
+            r = rn.rasterize(verts[f[:F]], 64)
+            ok = (r.edge_margin > 1e-4) & (r.depth_margin > 1e-5)
+            covered, left = int(r.alpha.sum()), int((r.alpha & ~ok).sum())
+            print(f"F {F} view {b}: covered {covered}, left out {left}, faces drawn {len(np.unique(r.face_idx)) - 1}, "
+                  f"highest {r.face_idx[ok].max()}")
+            assert covered >= 30 and left <= 0.01 * covered
+            last_drawn += int((r.face_idx[ok] == F - 1).sum())
+        assert last_drawn > 0                                                 # the last face of the last chunk is compared
+
+
 def wrap_render_color(verts, faces, colors, eye):
     """numpy fp32 restatement of what render_color (geom_utils.py:690-693), look_at (functional/look_at.py:59) with its identity
     axes, orthogonal (scale 1), the ambient-only lighting and face_vertices do before the kernel."""
