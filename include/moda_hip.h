@@ -542,6 +542,50 @@ int moda_icp_moments(const float* x0, const float* y, const int32_t* idx, const 
 int moda_sim3_apply(const float* x, const float* rts, int64_t B, int64_t N, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Bone re-initialisation and surface sampling on the rest mesh (moda_amd/csrc/bones_kernels.hip; additive entries of ABI 9: no
+ * existing signature changed).  None of these reads anything back; the caller reads `state` / `n_bad` when it needs them.
+ * ------------------------------------------------------------------------ */
+#define MODA_KMEANS_MAX_K 64         /* one lane of a wave per cluster */
+#define MODA_KMEANS_MAX_BLOCKS 1024  /* partials: MODA_KMEANS_MAX_BLOCKS * K * 4 doubles at most */
+
+/* The number of workgroups (rows of `partials`) a k-means iteration over N points uses: min(ceil(N / 256), MODA_KMEANS_MAX_BLOCKS). */
+int32_t moda_kmeans_blocks(int64_t N);
+
+/* moda_kmeans_steps: enqueues `steps` Lloyd iterations of k-means over x (N,3) fp32 (kmeans_pytorch.kmeans, as
+ * nnutils/geom_utils.py:885 reinit_bones calls it; two launches per iteration).  centers (K,3) fp32 holds the initial centres
+ * and is updated in place.  One iteration: assign[n] (int32) = the centre nearest to x[n] under
+ * d = fma(dz, dz, fma(dy, dy, dx * dx)) in fp32 with a strict <, so the lowest index among equal distances; per-cluster sums of
+ * x, y, z in float64 and counts in int32 through a fixed tree (per wave, per workgroup, then `partials`
+ * (moda_kmeans_blocks, K, 4) float64 added in block order: no float atomics, the same bits on every run);
+ * centre = float64 sum / count rounded to fp32 once; an EMPTY cluster k takes the point x[z % N], z = splitmix64(seed +
+ * 0x9E3779B97F4A7C15 * (i * K + k + 1)) with i the number of iterations finished before this one and splitmix64(z):
+ * z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31 (mod 2^64) -- the package draws
+ * a random point there; counts (K) int32 = the cluster sizes of this iteration; *shift = sum_k |centre_k - old centre_k|
+ * (float64, square roots added in index order).  state int32[2] = {iterations finished, done}: the caller zeroes it before
+ * the first call; an iteration increments state[0] and sets state[1] when shift^2 < tol or (iter_limit != 0 and state[0] >=
+ * iter_limit).  Iterations enqueued after `done` is set return at once and change nothing, so `assign` is the assignment
+ * against the centres BEFORE the last update, as the package returns it.
+ * MODA_EINVAL for K outside 1..MODA_KMEANS_MAX_K or a NULL pointer, MODA_ESHAPE for N < K or N >= 2^31. */
+int moda_kmeans_steps(const float* x, int64_t N, int32_t K, float* centers, int32_t* assign, double* partials, int32_t* counts,
+                      int32_t* state, double* shift, double tol, int32_t iter_limit, uint64_t seed, int32_t steps, void* stream);
+
+/* moda_mesh_face_cdf: the first two stages of pytorch3d.ops.sample_points_from_meshes (nnutils/moda.py:690).  verts (V,3)
+ * fp32, faces (F,3) int32.  areas (F) fp32 = 0.5 * |cross(b - a, c - a)|, every operation rounded in fp32; a face with an index
+ * outside [0, V) gets area 0, is counted in *n_bad (zeroed here) and is never read through: the caller must treat a nonzero
+ * count as an error.  cdf (F) float64 = the inclusive prefix sum of the areas, by tile sums, a scan of the tile sums and tile
+ * scans in a fixed order (no atomics).  Workspace tile_sum, tile_off: ceil(F / MODA_MC_SCAN_TILE) doubles each.
+ * MODA_ESHAPE for V < 1, F < 1, V >= 2^31 or 3 F >= 2^31. */
+int moda_mesh_face_cdf(const float* verts, const int32_t* faces, int64_t V, int64_t F, float* areas, double* cdf,
+                       double* tile_sum, double* tile_off, int64_t* n_bad, void* stream);
+
+/* moda_mesh_sample: the draw of pytorch3d.ops.sample_points_from_meshes from u (S,3) fp32 in [0, 1) and the outputs of
+ * moda_mesh_face_cdf.  face_idx[i] (int32) = the first face f with cdf[f] > u0 * cdf[F-1] (float64 product; binary search; a
+ * face of area 0 is never returned while any face has a positive area); s = sqrt(u1), w0 = 1 - s, w1 = s * (1 - u2),
+ * w2 = s * u2 in fp32; points[i] = fma(w2, c, fma(w1, b, w0 * a)) per coordinate.  S == 0 returns 0 and does nothing. */
+int moda_mesh_sample(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* areas, const double* cdf,
+                     const float* u, int64_t S, float* points, int32_t* face_idx, void* stream);
+
+/* ------------------------------------------------------------------------
  * Mesh rasteriser, forward only (moda_amd/csrc/raster_kernels.hip; additive entries of ABI 9: no existing signature changed).
  * The reference's soft_rasterize kernel (third_party/softras/soft_renderer/cuda/soft_rasterize_cuda_kernel.cu:246-483) in the
  * configuration of nnutils/moda.py:469-471: hard rgb aggregation, sigma_val 1e-12, prod alpha, vertex textures, both windings.

@@ -12,13 +12,15 @@ from .dual_quat import (q_normalize, q_mul, dq_mul, dq_normalize, dq_quaternion_
 from .loss_utils import (visibility_loss, compute_pts_exp, feat_match_loss, feat_match, kp_reproj_loss,  # noqa: F401
                          kp_reproj, eikonal_loss, nerf_gradient, compute_gradients_sdf)
 from .feeders import (raycast, sample_xy, chunk_rays, FrameCode, DQ_RTHead, correct_bones, correct_rest_pose,  # noqa: F401
-                      update_rays, update_delta_rts)
+                      update_rays, update_delta_rts, reinit_bones)
 from .mesh_queries import warp_bw, warp_fw, query_volume  # noqa: F401
 from . import mesh  # noqa: F401
 from .mesh import TriMesh, marching_cubes, largest_part, extract_mesh  # noqa: F401
 from . import mesh_eval  # noqa: F401
 from .mesh_eval import (nearest, chamfer_3DDist, fscore, iterative_closest_point, eval_mesh, ICPSolution,  # noqa: F401
                         SimilarityTransform)
+from . import bones  # noqa: F401
+from .bones import kmeans, sample_points_from_meshes, sample_surface, KMeansResult  # noqa: F401
 from . import mesh_render  # noqa: F401
 from . import soft_renderer  # noqa: F401
 from .mesh_render import rasterize, interpolate, render_dp, render_mesh  # noqa: F401

@@ -132,6 +132,11 @@ _SIGNATURES = {
     "moda_chamfer_bwd": (_c.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
     "moda_icp_moments": (_c.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
     "moda_sim3_apply": (_c.c_int, [_P, _P, _I64, _I64, _P, _P]),
+    # bone re-initialisation and surface sampling (bones_kernels.hip): additive entries of ABI 9
+    "moda_kmeans_blocks": (_I32, [_I64]),
+    "moda_kmeans_steps": (_c.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P, _P, _c.c_double, _I32, _c.c_uint64, _I32, _P]),
+    "moda_mesh_face_cdf": (_c.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "moda_mesh_sample": (_c.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P]),
     # mesh rasteriser (raster_kernels.hip): additive entries of ABI 9
     "moda_raster_fwd": (_c.c_int, [_P, _P, _I32, _I64, _I64, _I64, _I64, _F32, _F32, _I32] + [_P] * 7),
     "moda_raster_interp": (_c.c_int, [_P, _P, _I32, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),

@@ -189,6 +189,48 @@ def correct_bones(model, bones_rst, inverse=False, neudbs=True):
     return bone_transform(bones_rst, bone_rts_rst, neudbs, is_vec=True)[0], bone_rts_rst
 
 
+def reinit_bones(model, mesh, num_bones, neudbs):
+    """geom_utils.py:857-903: a fresh pose-head output layer for `num_bones` bones and bones placed at the k-means centres of
+    the mesh vertices, written into the existing parameters (none is added).  `mesh`: a TriMesh (its device vertices are used
+    as they are) or anything with `.vertices`."""
+    if not neudbs:
+        raise NotImplementedError("linear blend skinning: MoDA runs neudbs (moda.py:72-73)")
+    from .bones import kmeans
+    device = model.device
+    points = getattr(mesh, "vertices_t", None)
+    if points is None:
+        points = torch.as_tensor(np.asarray(mesh.vertices), dtype=torch.float32)
+    points = points.detach().to(device=device, dtype=torch.float32)                   # :867
+    rthead = model.nerf_body_rts[1].rgb
+    num_in = rthead[0].weight.shape[1]                                                # :871
+    rthead = nn.Sequential(nn.Linear(num_in, 7 * num_bones)).to(device)               # :873
+    torch.nn.init.xavier_uniform_(rthead[0].weight, gain=0.5)
+    torch.nn.init.zeros_(rthead[0].bias)
+    if points.shape[0] < 100:                                                         # :880-883
+        bound = torch.Tensor(np.asarray(model.latest_vars['obj_bound'], np.float32))[None]
+        center = torch.rand(num_bones, 3) * bound * 2 - bound
+    else:
+        _, center = kmeans(X=points, num_clusters=num_bones, iter_limit=100, tqdm_flag=False, distance='euclidean',
+                           device=device)                                             # :885-886
+    center = center.to(device)
+    orient = torch.Tensor([[1, 0, 0, 0]]).to(device)
+    orient = orient.repeat(num_bones, 1)
+    scale = torch.zeros(num_bones, 3).to(device)
+    bones = torch.cat([center, orient, scale], -1)                                    # :891
+
+    model.num_bones = num_bones
+    num_output = model.nerf_body_rts[1].num_output
+    bias_reinit = rthead[0].bias.data
+    weight_reinit = rthead[0].weight.data
+    model.nerf_body_rts[1].rgb[0].bias.data[:num_bones * num_output] = bias_reinit
+    model.nerf_body_rts[1].rgb[0].weight.data[:num_bones * num_output] = weight_reinit
+
+    bones, _ = correct_bones(model, bones, inverse=True, neudbs=neudbs)               # :900
+    model.bones.data[:num_bones] = bones.detach()
+    model.nerf_models['bones'] = model.bones
+    return
+
+
 def correct_rest_pose(opts, bone_rts_fw, bone_rts_rst, neudbs):
     """geom_utils.py:953-972: delta(J_b) = (J_b*)^-1 J_b for every frame's bone transforms."""
     if not neudbs:
