@@ -586,6 +586,33 @@ int moda_mesh_sample(const float* verts, const int32_t* faces, int64_t V, int64_
                      const float* u, int64_t S, float* points, int32_t* face_idx, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Gradient clipping between backward and the optimiser step (moda_amd/csrc/clip_kernels.hip; additive entry of ABI 9: no
+ * existing signature changed).  Reads nothing back and allocates nothing: it may run on a capturing stream.
+ * ------------------------------------------------------------------------ */
+#define MODA_CLIP_CHUNK 4096       /* floats per chunk: one 256-lane workgroup, four float4 per lane */
+
+/* moda_clip_grad: the reference trainer's clip_grad (nnutils/train_utils.py:1154-1311) over gradients that stay where they are,
+ * in three launches.  Every table is DEVICE memory.
+ * Segments (n_seg): seg_ptr[s] the fp32 gradient tensor (contiguous, 4-byte aligned; float4 accesses where it is 16-byte
+ * aligned), seg_numel[s] >= 1, seg_group[s] in 0..G-1 or -1 = ungrouped, seg_frozen[s] != 0 = this tensor alone is frozen.
+ * Chunks (n_chunks): chunk c covers elements [chunk_off[c], min(chunk_off[c] + MODA_CLIP_CHUNK, numel)) of segment
+ * chunk_seg[c]; the chunks of group g are [group_begin[g], group_begin[g + 1]) (group_begin: G + 1 entries), the ungrouped
+ * ones [group_begin[G], n_chunks).  A chunk whose entries do not describe a segment range is skipped, never followed.
+ * Per group: max_norm[g] fp32, frozen[g] != 0 = the stage freezes the group.
+ * Result: status int32[4] = {invalid, #NaN elements, #+-inf elements, 0} over ALL segments, frozen and ungrouped included
+ * (counts saturate at 2^31 - 1); norms[g] = (float)sqrt(sum of the fp32-rounded squares of the group's unfrozen elements,
+ * added in float64 in a fixed order: no float atomics, the same bits on every run), 0 for a frozen or empty group;
+ * coef[g] = fminf(1, max_norm[g] / (norms[g] + 1e-6f)) in fp32 (torch.nn.utils.clip_grad_norm_), 0 for a frozen group.
+ * Gradients: invalid -> EVERY segment is overwritten with zeros; else frozen chunks are overwritten with zeros, chunks of a
+ * group with coef != 1 become g * coef (one rounding), everything else -- ungrouped segments, coef == 1 -- is not written.
+ * Deviation from the reference, which tests isnan only: an infinite element rejects the step too (it would give coef 0 and
+ * inf * 0 = NaN).  Workspace: partial (n_chunks doubles), nonfinite (2 n_chunks int32).  n_chunks == 0 writes norms 0. */
+int moda_clip_grad(float* const* seg_ptr, const int64_t* seg_numel, const int32_t* seg_group, const uint8_t* seg_frozen,
+                   int32_t n_seg, const int32_t* chunk_seg, const int64_t* chunk_off, int32_t n_chunks,
+                   const int32_t* group_begin, int32_t G, const float* max_norm, const uint8_t* frozen, double* partial,
+                   int32_t* nonfinite, float* coef, float* norms, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------
  * Mesh rasteriser, forward only (moda_amd/csrc/raster_kernels.hip; additive entries of ABI 9: no existing signature changed).
  * The reference's soft_rasterize kernel (third_party/softras/soft_renderer/cuda/soft_rasterize_cuda_kernel.cu:246-483) in the
  * configuration of nnutils/moda.py:469-471: hard rgb aggregation, sigma_val 1e-12, prod alpha, vertex textures, both windings.

@@ -28,3 +28,5 @@ from .geom_utils import obj_to_cam, pinhole_cam, render_color, render_flow, mask
 from . import checkpoint  # noqa: F401
 from . import overflow  # noqa: F401
 from .autograd import set_train_precision, get_train_precision, GradBucket  # noqa: F401
+from . import train_utils  # noqa: F401
+from .train_utils import GradClipper, clip_grad, grad_group, GRAD_GROUPS  # noqa: F401

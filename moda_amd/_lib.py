@@ -140,6 +140,8 @@ _SIGNATURES = {
     # mesh rasteriser (raster_kernels.hip): additive entries of ABI 9
     "moda_raster_fwd": (_c.c_int, [_P, _P, _I32, _I64, _I64, _I64, _I64, _F32, _F32, _I32] + [_P] * 7),
     "moda_raster_interp": (_c.c_int, [_P, _P, _I32, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
+    # gradient clipping (clip_kernels.hip): additive entry of ABI 9
+    "moda_clip_grad": (_c.c_int, [_P, _P, _P, _P, _I32, _P, _P, _I32, _P, _I32] + [_P] * 8),
 }
 
 EXPORTS = tuple(_SIGNATURES)

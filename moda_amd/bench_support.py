@@ -82,11 +82,15 @@ class TrainHarness:
     `terms` (device, 8 floats) holds the weighted loss terms of the last step in TRAIN_TERMS order; `loss_buf` = [loss * N, N]."""
 
     def __init__(self, N=2048, S=128, B=25, precision="bf16", rank=0, world=1, dist=None, lr=2e-5, device=None, seed=1000,
-                 rays_per_frame=4, fused_adamw=True, bucket=True, use_fine=False, with_unc=False, strong=False):
+                 rays_per_frame=4, fused_adamw=True, bucket=True, use_fine=False, with_unc=False, strong=False, clip_grad=False,
+                 clip_scale=10.0):
         """use_fine / with_unc: the reference's LAST training stage (scripts/template.sh:59: --fine_steps 0 --use_unc): S/2 coarse
         depths rendered without gradients (rendering.py:91-107, here on the fused inference kernels in `PREPASS_PRECISION[precision]`),
         S/2 importance samples merged in, and the uncertainty network nerf_unc (8x256, moda.py:457-464) trained on
-        | sil * img_loss - unc_pred |^2 (moda.py:707-720) -- BASELINE configs[4] as a training step."""
+        | sil * img_loss - unc_pred |^2 (moda.py:707-720) -- BASELINE configs[4] as a training step.
+        clip_grad: the reference's stage between backward and the optimiser step (train_utils.py:966, :1154-1311) on the device
+        (moda_amd.train_utils.GradClipper, thresholds GRAD_GROUPS x clip_scale, the flag's default 10), after the gradient
+        exchange and mean and before `opt.step()`.  Off by default: the benchmarked step is forward + backward + AdamW."""
         from moda_amd import sharding
         global DEV
         # strong=True: ONE batch of N rays (the one-rank run's rays) cut into contiguous per-rank ranges (sharding.shard_rays), so
@@ -165,6 +169,25 @@ class TrainHarness:
         # that the backward kernels add into directly (moda_amd.GradBucket)
         self.want_bucket = bucket
         self.bucket = None
+        self.clip_grad, self.clip_scale = bool(clip_grad), float(clip_scale)
+        self.clipper = None
+
+    def named_params(self):
+        """`self.params` under the names the reference's model gives them (what clip_grad groups by): the networks by their
+        attribute names (nerf_coarse, nerf_skin, ...), the rest bones as `bones`."""
+        ref = {"coarse": "nerf_coarse"}
+        out = [(f"{ref.get(k, k)}.{n}", p) for k, m in self.models.items() if isinstance(m, torch.nn.Module)
+               for n, p in m.named_parameters()]
+        return out + [("bones", self.models["bones_rst"]), ("skin_aux", self.models["skin_aux"])]
+
+    def _clip(self):
+        """The clipping stage, if enabled: three launches, nothing read back (eager and captured alike)."""
+        if not self.clip_grad:
+            return
+        if self.clipper is None:
+            from moda_amd.train_utils import GradClipper
+            self.clipper = GradClipper(self.named_params(), self.clip_scale)
+        self.clipper()
 
     @staticmethod
     def _masked_mean(x, m):            # x[m].mean() without the boolean gather (no host sync, graph-capturable)
@@ -240,6 +263,7 @@ class TrainHarness:
         else:
             sharding.allreduce_gradients(self.params, self.dist, self.world)
             sharding.allreduce_sums(self.loss_buf, self.dist, self.world)
+        self._clip()
         self.opt.step()
         self.steps_done += 1
         return self.loss_buf
@@ -288,6 +312,7 @@ class TrainHarness:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 body()
+                self._clip()
                 self.opt.step()
             self.graph, self.graph_tail, self.graph_form = graph, None, "one graph"
             return graph
@@ -298,6 +323,7 @@ class TrainHarness:
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 body()
                 self.bucket.all_reduce(self.dist, self.world, force=True)
+                self._clip()
                 self.opt.step()
             self.graph, self.graph_tail, self.graph_form = graph, None, "one graph with the all-reduce inside"
             return graph
@@ -306,6 +332,7 @@ class TrainHarness:
             body()
         with torch.cuda.graph(tail, capture_error_mode="thread_local"):
             self.bucket.scale(self.world)
+            self._clip()
             self.opt.step()
         self.graph, self.graph_tail, self.graph_form = head, tail, "two graphs around one eager all-reduce"
         # the captures themselves execute nothing: parameters and optimiser state are those after `warm` steps
