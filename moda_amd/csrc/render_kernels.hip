@@ -621,9 +621,9 @@ __global__ __launch_bounds__(kBlock) void dqs_kernel(const float* __restrict__ d
 // Ray sampling (rendering.py:64-89, 112-113)
 // ------------------------------------------------------------------------------------------------
 DEVINL float z_at(float nr, float fr, long long s, long long S, int use_disp) {
-    // torch.linspace(0,1,S): step = 1/(S-1); values mirrored from the end for the upper half
+    // torch.linspace(0,1,S): step = 1/(S-1); values mirrored from the end for the upper half; a single value is the START (0)
     const float step = S > 1 ? 1.f / (float)(S - 1) : 0.f;
-    const float t = (s < S / 2) ? step * (float)s : 1.f - step * (float)(S - 1 - s);
+    const float t = (s < S / 2 || S == 1) ? step * (float)s : 1.f - step * (float)(S - 1 - s);
     return use_disp ? 1.f / (1.f / nr * (1.f - t) + 1.f / fr * t) : nr * (1.f - t) + fr * t;
 }
 
@@ -812,7 +812,7 @@ __global__ __launch_bounds__(kBlock) void sample_pdf_kernel(const float* __restr
         if (u) uu = u[n * n_imp + k];
         else {                                                                            // :604 linspace(0,1,n_imp)
             const float step = n_imp > 1 ? 1.f / (float)(n_imp - 1) : 0.f;
-            uu = (k < n_imp / 2) ? step * (float)k : 1.f - step * (float)(n_imp - 1 - k);
+            uu = (k < n_imp / 2 || n_imp == 1) ? step * (float)k : 1.f - step * (float)(n_imp - 1 - k);   // one sample: u = 0
         }
         // searchsorted(cdf, u, right=True): number of cdf entries <= u   (:610)
         int lo = 0, hi = nb;
