@@ -344,7 +344,7 @@ def composite(rgbs, sigmas, feat, z_vals, rays_d, beta, noise=None, oob=None, vi
     """
     dt = z_vals.dtype
     deltas = z_vals[:, 1:] - z_vals[:, :-1]
-    deltas = np.concatenate([deltas, np.full_like(deltas[:, :1], 1e10)], -1)
+    deltas = np.concatenate([deltas, np.full_like(z_vals[:, :1], 1e10)], -1)                  # (z_vals: a ray of ONE sample has no delta to copy)
     deltas = deltas * np.sqrt((rays_d * rays_d).sum(-1))[:, None]
     semantic = dt.type(rgb_filter_scale) * _sigmoid(dt.type(-10) * sigmas)      # :171 (before the noise is added)
     if noise is not None:

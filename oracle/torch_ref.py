@@ -161,7 +161,7 @@ def dqs(dq, skin, pts):
 def composite(rgbs, sigmas, feat, z_vals, rays_d, beta, noise=None, rgb_filter_scale=0.0):
     """rendering.py:183-237; rgb_filter_scale > 0 is opts.rgb_filter with scale_rgb (:171, 225-230)"""
     deltas = z_vals[:, 1:] - z_vals[:, :-1]
-    deltas = torch.cat([deltas, torch.full_like(deltas[:, :1], 1e10)], -1) * rays_d.norm(dim=-1, keepdim=True)
+    deltas = torch.cat([deltas, torch.full_like(z_vals[:, :1], 1e10)], -1) * rays_d.norm(dim=-1, keepdim=True)
     semantic = rgb_filter_scale * torch.sigmoid(-10 * sigmas)
     if noise is not None:
         sigmas = sigmas + noise
