@@ -850,6 +850,61 @@ typedef struct {
 } moda_loss_term;
 int moda_loss_terms(const moda_loss_term* terms, int32_t n_terms, float* out, const float* g, void* stream);
 
+/* ---- the loss stage with the reference's default flags (loss_flt, rm_novp, root_sm; lossasm_kernels.hip): additive entries of
+ * ABI 9.  Nothing here allocates or synchronises; every launch goes to `stream`, so the calls can be captured into a graph. ---- */
+
+/* Frame rejection by silhouette error, line-loaded data (nnutils/loss_utils.py:432-445 loss_filter_line).  values (N) the weighted
+ * per-ray silhouette loss; errid, frameid (N) int32, or int64 where the *64 argument is non-zero; sil_err (num_frames * img_size)
+ * the persistent state.  sil_err[errid[i]] = values[i], the HIGHEST i winning a repeated id; per frame mean = row sum /
+ * (1e-9 + #positive) in float64; median over the frames with mean > 0 (numpy's: two middle values averaged, NaN for none);
+ * invalid[i] = mean[frameid[i]] > median * scale_factor (float64, strict; NaN flags nothing).  An id outside its table is skipped
+ * and counted.  status (4 int32) = [#ids out of range, #invalid rays, #frames with mean > 0, 0].
+ * ws: moda_loss_filter_ws_bytes(num_frames, img_size) bytes, 8-byte aligned, every byte 0xff before the FIRST call; the calls
+ * leave it ready for the next.  num_frames <= 8000 (the means are ranked in LDS by one workgroup).  Three launches; the bits do not depend on scheduling. */
+int64_t moda_loss_filter_ws_bytes(int64_t num_frames, int64_t img_size);
+int moda_loss_filter_line(const float* values, const void* errid, int32_t errid64, const void* frameid, int32_t frameid64,
+                          int64_t N, float* sil_err, int64_t num_frames, int64_t img_size, double scale_factor, void* ws,
+                          uint8_t* invalid, int32_t* status, void* stream);
+
+/* The same for whole-frame batches (loss_utils.py:447-476 loss_filter and the update of nnutils/moda.py:533).  x (bs, n) values,
+ * mask (bs, n) float, or uint8 / bool where mask_u8; state (num_frames) the per-frame history; errid (bs).
+ * flo_err[b] = (float)sum_j x * mask / (1e-9f + (float)sum_j mask), the sums in float64; invalid[b] = flo_err[b] > median of the
+ * positive history * scale_factor in float64 -- the history BEFORE this call; then state[errid[b]] = flo_err[b] (highest b wins).
+ * status as above.  bs <= 4096, num_frames <= 8000.  One launch. */
+int moda_loss_filter_frame(const float* x, const void* mask, int32_t mask_u8, int64_t bs, int64_t n, float* state,
+                           int64_t num_frames, const void* errid, int32_t errid64, double scale_factor, float* flo_err,
+                           uint8_t* invalid, int32_t* status, void* stream);
+
+/* Second-order smoothness of the root poses (loss_utils.py:486-517 compute_root_sm_2nd_loss, geom_utils.py:1196-1205 rot_angle).
+ * rtk (T, rows, 4), rows 3 or 4, 16-byte aligned; offsets (n_videos + 1) DEVICE int32, non-decreasing, within [0, T]: video v is
+ * the frames [offsets[v], offsets[v + 1]).  Over every three consecutive frames of one video: angle = acos(clamp((tr((R0 R1^T)
+ * (R1 R2^T)^T) - 1) / 2, -1 + 1e-4, 1 - 1e-4)), trn = |(t0 - t1) - (t1 - t2)|, products and sums in fp32, the means in float64.
+ * g == NULL, forward: out4 = [0.1 * (0.1 * mean angle + mean trn), 0.1 * mean angle, mean trn, #triples] (NaN without a triple).
+ * g != NULL, backward: drtk (T, rows, 4) = g[0] * d out4[0] / d rtk, every element written, one thread per frame and no atomics;
+ * zero through a clamped cosine (a cosine AT a bound passes, as torch's clamp) and at trn == 0. */
+int moda_root_sm(const float* rtk, int32_t rows, int64_t T, const int32_t* offsets, int32_t n_videos, float* out4, const float* g,
+                 float* drtk, void* stream);
+
+/* The loss assembly of banmo.forward_default with every branch (nnutils/moda.py:517-768).  Term t: the rows of x (n, k) selected
+ * by mask (kinds as moda_loss_term), each element multiplied by keep = (drop[row] ? 0 : 1) and then by scale[row] (either may be
+ * NULL: no product) -- products, so a NaN in a dropped row stays NaN; mean_t = sum / (k * #selected), dropped rows counted.
+ * total <- carry_t * total + weight_t * mean_t in term order from 0, then total * total_wt.  `terms` is a HOST array, <= 16.
+ * g == NULL, forward: out (1 + 3 n_terms) = [total, weight_t * mean_t ..., den_t ..., mean_t ...].
+ * g != NULL, backward: dx_t (n, k) = g[0] * total_wt * weight_t * prod_{s > t} carry_s / den_t * scale * keep on the selected rows,
+ * 0 elsewhere, for every term with dx != NULL (x may be NULL); nothing flows into scale.  One launch each way.  Without scale,
+ * drop, carry != 1 and total_wt != 1 the values are moda_loss_terms' bit for bit. */
+typedef struct {
+    const float* x;
+    const void* mask;
+    const float* scale;
+    const uint8_t* drop;
+    float* dx;
+    int64_t n;
+    int32_t k, mask_kind;
+    float weight, carry;
+} moda_asm_term;
+int moda_loss_assembly(const moda_asm_term* terms, int32_t n_terms, float total_wt, float* out, const float* g, void* stream);
+
 /* S3IM, opts.s3im_loss (nnutils/loss_utils.py:575-702 S3IM.forward + SSIM(window 4, stride 4) / _ssim; called at
  * nnutils/rendering.py:528-532):  loss[0] = 1 - mean SSIM over the Gaussian 4x4 / stride 4 / padding 1 windows of the
  * (3, patch_h, patch_w_total) virtual patch whose pixel (h, w) holds row index[h * patch_w_total + w] % N of rgb * mask and of

@@ -29,6 +29,11 @@ class LossTerm(_c.Structure):       # moda_hip.h moda_loss_term
                 ("reserved", _I32)]
 
 
+class AsmTerm(_c.Structure):        # moda_hip.h moda_asm_term
+    _fields_ = [("x", _P), ("mask", _P), ("scale", _P), ("drop", _P), ("dx", _P), ("n", _I64), ("k", _I32), ("mask_kind", _I32),
+                ("weight", _F32), ("carry", _F32)]
+
+
 class NerfTrainDesc(_c.Structure):
     _fields_ = [("D", _I32), ("W", _I32), ("P", _I32), ("C1", _I32), ("Cd", _I32), ("n_out", _I32), ("raw_feat", _I32),
                 ("sigma_only", _I32), ("n_freq", _I32), ("reserved", _I32), ("window", _F32 * 16), ("M", _I64), ("R1", _I64),
@@ -142,6 +147,12 @@ _SIGNATURES = {
     "moda_raster_interp": (_c.c_int, [_P, _P, _I32, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
     # gradient clipping (clip_kernels.hip): additive entry of ABI 9
     "moda_clip_grad": (_c.c_int, [_P, _P, _P, _P, _I32, _P, _P, _I32, _P, _I32] + [_P] * 8),
+    # loss filter, root smoothness, full loss assembly (lossasm_kernels.hip): additive entries of ABI 9
+    "moda_loss_filter_ws_bytes": (_I64, [_I64, _I64]),
+    "moda_loss_filter_line": (_c.c_int, [_P, _P, _I32, _P, _I32, _I64, _P, _I64, _I64, _c.c_double, _P, _P, _P, _P]),
+    "moda_loss_filter_frame": (_c.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _P, _I32, _c.c_double, _P, _P, _P, _P]),
+    "moda_root_sm": (_c.c_int, [_P, _I32, _I64, _P, _I32, _P, _P, _P, _P]),
+    "moda_loss_assembly": (_c.c_int, [_P, _I32, _F32, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

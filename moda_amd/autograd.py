@@ -816,6 +816,101 @@ class LossTermsFn(Function):
         return (None,) + tuple(None if d is None else d.view(sh) for d, sh in zip(dxs, ctx.shapes))
 
 
+class LossAssemblyFn(Function):
+    """The loss assembly of moda.py:517-768 with its filter, rm_novp and warm-up branches, one launch each way
+    (moda_loss_assembly): total <- carry_t * total + weight_t * mean_t in term order, times total_wt.
+    spec: one (weight, mask, kind, scale, drop, carry) per value tensor -- mask / kind as LossTermsFn; scale None or a float
+    tensor with one entry per row (taken detached: nothing flows into it); drop None or a bool / uint8 tensor per row.
+    -> (total 0-dim, rest (3 T,) detached = [weighted terms, denominators, unweighted means])."""
+
+    @staticmethod
+    def forward(ctx, spec, total_wt, *xs):
+        T = len(xs)
+        if not 1 <= T <= 16:
+            raise ValueError(f"moda_loss_assembly takes 1..16 terms, got {T}")
+        dev = xs[0].device
+        out = torch.empty((1 + 3 * T,), device=dev)
+        arr = (L.AsmTerm * T)()
+        keep = []
+        for t, (x, (w, mask, kind, scale, drop, carry)) in enumerate(zip(xs, spec)):
+            x2 = _f32(x)
+            n = x2.shape[0] if x2.dim() > 0 else 1
+            mk, mp = 0, None
+            if mask is not None:
+                if kind == "bool":
+                    m = mask.reshape(-1).contiguous()
+                    if m.dtype != torch.bool:
+                        raise TypeError("kind 'bool' needs a bool mask")
+                    mk = 2
+                else:
+                    m = _f32(mask).reshape(-1)
+                    mk = 1
+                n = m.numel()
+                mp = L.ptr(m)
+                keep.append(m)
+            if x2.numel() == 0 or x2.numel() % n:
+                raise ValueError(f"term {t}: {x2.numel()} values do not make {n} rows")
+            x2 = x2.reshape(n, -1)
+            sp = dp = None
+            if scale is not None:
+                sc = _f32(scale.detach()).reshape(-1)
+                if sc.numel() != n:
+                    raise ValueError(f"term {t}: {n} rows but a scale of {sc.numel()}")
+                sp = L.ptr(sc)
+                keep.append(sc)
+            if drop is not None:
+                dr = drop.reshape(-1).contiguous()
+                if dr.dtype not in (torch.bool, torch.uint8) or dr.numel() != n:
+                    raise ValueError(f"term {t}: drop must hold {n} bool / uint8 entries")
+                dp = L.ptr(dr)
+                keep.append(dr)
+            keep.append(x2)
+            arr[t] = L.AsmTerm(x=L.ptr(x2), mask=mp, scale=sp, drop=dp, dx=None, n=n, k=x2.shape[1], mask_kind=mk,
+                               weight=float(w), carry=float(carry))
+        L.call("moda_loss_assembly", arr, T, float(total_wt), L.ptr(out), None, L.stream())
+        ctx.arr, ctx.keep, ctx.shapes, ctx.T, ctx.total_wt = arr, keep, [tuple(x.shape) for x in xs], T, float(total_wt)
+        ctx.save_for_backward(out)
+        total, rest = out[0], out[1:]
+        ctx.mark_non_differentiable(rest)
+        return total, rest
+
+    @staticmethod
+    def backward(ctx, g, _g_out):
+        out, = ctx.saved_tensors
+        dxs = []
+        for t in range(ctx.T):
+            need = ctx.needs_input_grad[2 + t]
+            dx = torch.empty((ctx.arr[t].n, ctx.arr[t].k), device=out.device) if need else None
+            ctx.arr[t].dx = L.ptr(dx)
+            dxs.append(dx)
+        L.call("moda_loss_assembly", ctx.arr, ctx.T, ctx.total_wt, L.ptr(out), L.ptr(_f32(g).reshape(1)), L.stream())
+        return (None, None) + tuple(None if d is None else d.view(sh) for d, sh in zip(dxs, ctx.shapes))
+
+
+class RootSmFn(Function):
+    """compute_root_sm_2nd_loss (loss_utils.py:486-517) over rtk (T, 3 | 4, 4) and the device table of video offsets (V + 1,)
+    int32: one kernel forward, one gather kernel backward (moda_root_sm).  -> (loss 0-dim, parts (3,) detached =
+    [0.1 mean angle, mean trn, #triples])."""
+
+    @staticmethod
+    def forward(ctx, rtk, offsets):
+        r = _f32(rtk)
+        out = torch.empty((4,), device=r.device)
+        L.call("moda_root_sm", L.ptr(r), r.shape[1], r.shape[0], L.ptr(offsets), offsets.numel() - 1, L.ptr(out), None, None, L.stream())
+        ctx.save_for_backward(r, offsets, out)
+        parts = out[1:]
+        ctx.mark_non_differentiable(parts)
+        return out[0], parts
+
+    @staticmethod
+    def backward(ctx, g, _g_out):
+        r, offsets, out = ctx.saved_tensors
+        d = torch.empty_like(r)
+        L.call("moda_root_sm", L.ptr(r), r.shape[1], r.shape[0], L.ptr(offsets), offsets.numel() - 1, L.ptr(out),
+               L.ptr(_f32(g).reshape(1)), L.ptr(d), L.stream())
+        return d, None
+
+
 class S3imFn(Function):
     """S3IM.forward on already gathered index tables (loss_utils.py:575-702): 1 - mean SSIM of the (3, H, Wt) virtual patch.
     rgb (N,3) rendered colours, tar (N,3) observed colours, mask (N,1); index (H*Wt,) int32."""

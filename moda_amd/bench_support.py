@@ -83,14 +83,18 @@ class TrainHarness:
 
     def __init__(self, N=2048, S=128, B=25, precision="bf16", rank=0, world=1, dist=None, lr=2e-5, device=None, seed=1000,
                  rays_per_frame=4, fused_adamw=True, bucket=True, use_fine=False, with_unc=False, strong=False, clip_grad=False,
-                 clip_scale=10.0):
+                 clip_scale=10.0, default_losses=False):
         """use_fine / with_unc: the reference's LAST training stage (scripts/template.sh:59: --fine_steps 0 --use_unc): S/2 coarse
         depths rendered without gradients (rendering.py:91-107, here on the fused inference kernels in `PREPASS_PRECISION[precision]`),
         S/2 importance samples merged in, and the uncertainty network nerf_unc (8x256, moda.py:457-464) trained on
         | sil * img_loss - unc_pred |^2 (moda.py:707-720) -- BASELINE configs[4] as a training step.
         clip_grad: the reference's stage between backward and the optimiser step (train_utils.py:966, :1154-1311) on the device
         (moda_amd.train_utils.GradClipper, thresholds GRAD_GROUPS x clip_scale, the flag's default 10), after the gradient
-        exchange and mean and before `opt.step()`.  Off by default: the benchmarked step is forward + backward + AdamW."""
+        exchange and mean and before `opt.step()`.  Off by default: the benchmarked step is forward + backward + AdamW.
+        default_losses: assemble the loss as the reference's default flags do (moda.py:167-168 loss_flt, rm_novp) through
+        moda_amd.loss_utils.forward_loss with a device-resident LossFilter in line mode: ray i belongs to frame
+        i // rays_per_frame and to line i % rays_per_frame of it.  root_sm stays off (the synthetic scene has no camera table).
+        Off by default: the default path and the benchmarked step are unchanged."""
         from moda_amd import sharding
         global DEV
         # strong=True: ONE batch of N rays (the one-rank run's rays) cut into contiguous per-rank ranges (sharding.shard_rays), so
@@ -171,6 +175,19 @@ class TrainHarness:
         self.bucket = None
         self.clip_grad, self.clip_scale = bool(clip_grad), float(clip_scale)
         self.clipper = None
+        self.default_losses = bool(default_losses)
+        self.loss_filter = None
+        if self.default_losses:
+            from moda_amd.loss_utils import LossFilter
+            n_frames = (N + rays_per_frame - 1) // rays_per_frame
+            self.loss_filter = LossFilter(n_frames, 512, lineload=True, device=self.dev)
+            idx = torch.arange(N, device=self.dev)
+            self.frameid = (idx // rays_per_frame).to(torch.int32)
+            self.errid = self.frameid * 512 + (idx % rays_per_frame).to(torch.int32)
+            w = TRAIN_WEIGHTS
+            self.loss_opts = dict(loss_flt=True, rm_novp=True, root_sm=False, bone_loc_reg=0.0, lineload=True, use_unc=self.with_unc,
+                                  img_wt=w["img_wt"], sil_wt=w["sil_wt"], frnd_wt=w["frnd_wt"], flow_wt=w["flow_wt"],
+                                  feat_wt=w["feat_wt"], proj_wt=w["proj_wt"], cyc_wt=w["cyc_wt"])
 
     def named_params(self):
         """`self.params` under the names the reference's model gives them (what clip_grad groups by): the networks by their
@@ -212,11 +229,25 @@ class TrainHarness:
                                           "noise_raw": self.noise_raw, "pdf_u": self.pdf_u, "noise_raw_pre": self.noise_pre})
         # moda.py:540-705 as one launch each way; these weights (not the flags' defaults) keep every term of the synthetic scene
         # within two orders of magnitude of the others, and the loss values comparable across rounds
+        if self.default_losses:
+            return self._fwd_bwd_default_losses(r)
         loss, terms = total_loss(r, TRAIN_WEIGHTS)
         if self.with_unc:
             loss = loss + unc_loss(r)                                  # moda.py:707-720
         loss.backward()
         self.terms.copy_(torch.stack([terms[k] for k in TRAIN_TERMS]))
+        return loss.detach()
+
+    def _fwd_bwd_default_losses(self, r):
+        """moda.py:517-768 with loss_flt and rm_novp: the filter's three launches, the assembly's one each way, nothing read back.
+        `progress` is 1 (past warmup_steps: the silhouette term is filtered too); the visibility term carries the reference's
+        0.01 (moda.py:702), not TRAIN_WEIGHTS' vis_wt.  `terms` keeps TRAIN_TERMS' order; its cycle entry is weighted."""
+        from moda_amd.loss_utils import forward_loss
+        loss, aux = forward_loss(r, self.loss_opts, loss_filter=self.loss_filter, errid=self.errid, frameid=self.frameid, progress=1.0)
+        loss.backward()
+        keys = ("img_loss", "sil_loss", "feat_rnd_loss", "flo_loss", "feat_loss", "proj_loss", "visibility_loss", "cyc_loss")
+        self.terms.copy_(torch.stack([aux[k] for k in keys]))
+        self.terms[7].mul_(TRAIN_WEIGHTS["cyc_wt"])
         return loss.detach()
 
     def zero_grad(self):

@@ -251,6 +251,18 @@ def obj_to_cam(in_verts, Rmat, Tmat):
     return verts.reshape(in_verts.shape)
 
 
+def rot_angle(mat):
+    """geom_utils.py:1196-1205: rotation angle of mat (..., 3, 3) = acos(clamp((trace - 1) / 2, -1 + 1e-4, 1 - 1e-4)).  The
+    stand-alone helper, plain torch on a device tensor; the training step's use of it lies inside moda_root_sm
+    (loss_utils.compute_root_sm_2nd_loss)."""
+    eps = 1e-4
+    if not torch.is_tensor(mat):
+        raise TypeError(f"rot_angle: expected a tensor, got {type(mat)}")
+    mat = L.dev(mat, mat.dtype)
+    cos = (mat[..., 0, 0] + mat[..., 1, 1] + mat[..., 2, 2] - 1) / 2
+    return torch.acos(cos.clamp(-1 + eps, 1 - eps))
+
+
 def K2mat(K):
     """geom_utils.py:596-612: K (...,4) = fx, fy, px, py -> (bs,3,3)."""
     K = K.view(-1, 4)

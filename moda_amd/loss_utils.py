@@ -260,10 +260,11 @@ LOSS_TERMS = ("img", "sil", "frnd", "flo", "feat", "proj", "vis", "cyc")
 
 
 def total_loss(rendered, weights=None):
-    """The total loss of banmo.forward_default over render_rays' result dict (moda.py:540-705), default configuration (no
-    loss_flt / rm_novp / warm-up branches): img_wt * img_loss_samp[sil > 0].mean() + sil_wt * sil_loss_samp[vis > 0].mean() +
+    """The loss assembly of banmo.forward_default over render_rays' result dict (moda.py:540-705) in a REDUCED configuration:
+    loss_flt, rm_novp and root_sm off and no warm-up branch -- the reference itself trains with all three on (moda.py:164-168;
+    `forward_loss` below is that assembly).  img_wt * img_loss_samp[sil > 0].mean() + sil_wt * sil_loss_samp[vis > 0].mean() +
     frnd_wt * frnd_loss_samp[sil > 0].mean() + 2 flow_wt * flo_loss_samp[sil_at_samp_flo].mean() + feat_wt * feat_err[sil > 0]
-    .mean() + proj_wt * proj_err[sil > 0].mean() + cyc_wt * frame_cyc_dis.mean() + vis_wt * vis_loss -- the terms whose keys
+    .mean() + proj_wt * proj_err[sil > 0].mean() + vis_wt * vis_loss + cyc_wt * frame_cyc_dis.mean() -- the terms whose keys
     the dict holds, as ONE launch forward and one backward (moda_loss_terms) instead of ~55 eager ops with a boolean gather
     (and its host sync) per term.  -> (total, {term name: weighted term, detached}).  moda.py itself cannot be imported here
     (absl, mcubes ...): restated from the cited lines, checked against the plain-torch restatement (oracle/torch_ref.py)."""
@@ -285,10 +286,302 @@ def total_loss(rendered, weights=None):
     return total, {n: terms[i] for i, n in enumerate(names)}
 
 
-def unc_loss(rendered):
+# ---- the stage between render_rays and backward() with the reference's own flags (loss_flt, rm_novp, root_sm) ------------------
+def _ids(t, device, what):
+    """errid / frameid as the kernels read them: a contiguous int32 or int64 device tensor.  A host tensor is copied (once per
+    call: not capturable -- keep the ids on the device, as pixel_lines.set_input leaves them)."""
+    if not torch.is_tensor(t):
+        t = torch.as_tensor(np.asarray(t))
+    if t.dtype not in (torch.int32, torch.int64):
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise TypeError(f"{what} must be an integer tensor, got {t.dtype}")
+        t = t.to(torch.int64)
+    if t.device != device:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{what} lies on {t.device}: copying it is not capturable, pass a device tensor")
+        t = t.to(device)
+    return t.reshape(-1).contiguous()
+
+
+def _filter_ws(num_frames, img_size, device):
+    nbytes = L.load().moda_loss_filter_ws_bytes(num_frames, img_size)
+    return torch.full((nbytes,), 255, dtype=torch.uint8, device=device)        # every owner word -1: no slot claimed
+
+
+def _filter_line(values, errid, frameid, sil_err, num_frames, img_size, scale_factor, ws, invalid, status):
+    dev = sil_err.device
+    v = L.dev(values.detach()).reshape(-1)
+    e, f = _ids(errid, dev, "errid"), _ids(frameid, dev, "frameid")
+    if e.numel() != v.numel() or f.numel() != v.numel():
+        raise ValueError(f"loss_filter_line: {v.numel()} values, {e.numel()} errid, {f.numel()} frameid")
+    if invalid is None:
+        invalid = torch.empty((v.numel(),), dtype=torch.bool, device=dev)
+    L.call("moda_loss_filter_line", L.ptr(v), L.ptr(e), int(e.dtype == torch.int64), L.ptr(f), int(f.dtype == torch.int64), v.numel(),
+           L.ptr(sil_err), num_frames, img_size, float(scale_factor), L.ptr(ws), L.ptr(invalid), L.ptr(status), L.stream())
+    return invalid
+
+
+def _filter_frame(x, mask, state, errid, scale_factor, status):
+    dev = state.device
+    bs = mask.shape[0]
+    xv = L.dev(x.detach()).reshape(bs, -1)
+    m = mask.reshape(bs, -1)
+    m = m.contiguous() if m.dtype in (torch.bool, torch.uint8) else L.dev(m)
+    if m.device != dev or m.shape != xv.shape:
+        raise ValueError(f"loss_filter: values {tuple(xv.shape)} and mask {tuple(m.shape)} on {m.device}")
+    e = _ids(errid, dev, "errid")
+    if e.numel() != bs:
+        raise ValueError(f"loss_filter: {bs} batch rows, {e.numel()} errid")
+    flo_err = torch.empty((bs,), device=dev)
+    invalid = torch.empty((bs,), dtype=torch.bool, device=dev)
+    L.call("moda_loss_filter_frame", L.ptr(xv), L.ptr(m), int(m.dtype != torch.float32), bs, xv.shape[1], L.ptr(state), state.numel(),
+           L.ptr(e), int(e.dtype == torch.int64), float(scale_factor), L.ptr(flo_err), L.ptr(invalid), L.ptr(status), L.stream())
+    return flo_err, invalid
+
+
+def _check_state(t, numel, what):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
+        raise ValueError(f"{what}: the state must be a contiguous fp32 device tensor of {numel} entries (the reference's numpy "
+                         "array holds fp32 values: nothing is lost)")
+
+
+MAX_FILTER_FRAMES = 8000        # include/moda_hip.h: moda_loss_filter_line / _frame
+
+
+class LossFilter:
+    """The frame rejection of moda.py:522-538 with its state -- the reference's `latest_vars['sil_err']` -- on the device.
+    lineload=True  (loss_utils.py:432-445 loss_filter_line): state `sil_err` (num_frames * img_size,) fp32;
+                   flt(sil_loss_weighted (N, ...), errid (N,), frameid (N,)) -> invalid (N,) bool.
+    lineload=False (loss_utils.py:447-476 loss_filter + the update of moda.py:533): state (num_frames,);
+                   flt(sil_loss_weighted (bs, n, ...), errid (bs,), mask=None (bs, n, ...)) -> invalid (bs,) bool; mask None is
+                   the reference's `sil_at_samp > -1`, every ray.  `flt.flo_err` holds the batch's per-frame errors.
+    The call enqueues three launches (one in frame mode) on the current stream, allocates only through torch's allocator and
+    reads nothing back: it can be captured.  `status` (4,) int32 = [#ids out of range (skipped), #invalid rays, #frames with
+    history, 0] stands for the reference's `print('%d removed from sil')`.  `reset()` is the per-epoch zeroing of
+    train_utils.py:1120.  errid / frameid: int32 or int64 device tensors."""
+
+    def __init__(self, num_frames, img_size, lineload=True, scale_factor=10, device="cuda"):
+        self.num_frames, self.img_size, self.lineload, self.scale_factor = int(num_frames), int(img_size), bool(lineload), scale_factor
+        dev = torch.device(device)
+        if not 1 <= self.num_frames <= MAX_FILTER_FRAMES:
+            raise ValueError(f"LossFilter: num_frames must lie in 1..{MAX_FILTER_FRAMES} (the medians are ranked in one workgroup's LDS)")
+        if dev.type != "cuda":
+            raise RuntimeError("LossFilter lives on a CUDA (ROCm) device; the HIP library is the only compute path")
+        self.sil_err = torch.zeros((self.num_frames * self.img_size if self.lineload else self.num_frames,), device=dev)
+        self.status = torch.zeros((4,), dtype=torch.int32, device=dev)
+        self.flo_err = None
+        self._ws = _filter_ws(self.num_frames, self.img_size, dev) if self.lineload else None
+
+    def reset(self):
+        self.sil_err.zero_()
+
+    def __call__(self, sil_loss_weighted, errid, frameid=None, mask=None):
+        if self.lineload:
+            if frameid is None:
+                raise ValueError("LossFilter(lineload=True) takes errid and frameid")
+            return _filter_line(sil_loss_weighted, errid, frameid, self.sil_err, self.num_frames, self.img_size, self.scale_factor,
+                                self._ws, None, self.status)
+        if mask is None:
+            mask = torch.ones(sil_loss_weighted.shape, dtype=torch.bool, device=self.sil_err.device)
+        self.flo_err, invalid = _filter_frame(sil_loss_weighted, mask, self.sil_err, errid, self.scale_factor, self.status)
+        return invalid
+
+
+def loss_filter_line(sil_err, errid, frameid, sil_loss_samp, img_size, scale_factor=10):
+    """loss_utils.py:432-445 with the reference's signature; `sil_err` a contiguous fp32 DEVICE tensor of num_frames * img_size
+    entries, updated in place as the reference updates its array.  -> invalid (N,) bool, on the device."""
+    if not torch.is_tensor(sil_err) or sil_err.numel() % int(img_size):
+        raise ValueError("loss_filter_line: sil_err must be a device tensor of num_frames * img_size entries")
+    _check_state(sil_err, sil_err.numel(), "loss_filter_line")
+    T = sil_err.numel() // int(img_size)
+    status = torch.empty((4,), dtype=torch.int32, device=sil_err.device)
+    return _filter_line(sil_loss_samp, errid, frameid, sil_err, T, int(img_size), scale_factor,
+                        _filter_ws(T, int(img_size), sil_err.device), None, status)
+
+
+def loss_filter(g_floerr, flo_loss_samp, sil_at_samp_flo, scale_factor=10):
+    """loss_utils.py:447-476 with the reference's signature; `g_floerr` the (T,) fp32 device history, NOT updated (the caller
+    assigns `g_floerr[errid] = flo_err`, moda.py:533).  -> (flo_err (bs,), invalid (bs,) bool), device tensors."""
+    _check_state(g_floerr, g_floerr.numel() if torch.is_tensor(g_floerr) else -1, "loss_filter")
+    bs = sil_at_samp_flo.shape[0]
+    status = torch.empty((4,), dtype=torch.int32, device=g_floerr.device)
+    none = torch.full((bs,), -1, dtype=torch.int32, device=g_floerr.device)     # ids outside the table: no update
+    return _filter_frame(flo_loss_samp, sil_at_samp_flo, g_floerr, none, scale_factor, status)
+
+
+_OFFSETS = {}
+
+
+def _offset_table(data_offset, T, device):
+    """The videos' frame ranges as a device int32 table, uploaded once per distinct tuple."""
+    off = tuple(int(v) for v in (data_offset.tolist() if hasattr(data_offset, "tolist") else data_offset))
+    if len(off) < 2 or off[0] < 0 or off[-1] > T or any(b < a for a, b in zip(off, off[1:])):
+        raise ValueError(f"data_offset {off}: expected non-decreasing frame indices within [0, {T}]")
+    key = (off, str(device))
+    t = _OFFSETS.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("compute_root_sm_2nd_loss: a new data_offset is uploaded from the host -- call once before capture")
+        t = torch.tensor(off, dtype=torch.int32).to(device)
+        _OFFSETS[key] = t
+    return t
+
+
+def root_sm_parts(rtk_all, data_offset):
+    """-> (loss, parts (3,) detached = [0.1 * mean angle, mean trn, #triples]) of compute_root_sm_2nd_loss."""
+    r = L.dev(rtk_all)
+    if r.dim() != 3 or r.shape[1] not in (3, 4) or r.shape[2] != 4:
+        raise ValueError(f"rtk_all: expected (T, 4, 4) or (T, 3, 4), got {tuple(r.shape)}")
+    return A.RootSmFn.apply(r, _offset_table(data_offset, r.shape[0], r.device))
+
+
+def compute_root_sm_2nd_loss(rtk_all, data_offset):
+    """loss_utils.py:486-517: 0.1 * (0.1 * mean rot_angle((R0 R1^T)(R1 R2^T)^T) + mean |(t0 - t1) - (t1 - t2)|) over the
+    consecutive frame triples of every video [data_offset[v], data_offset[v + 1]); NaN when no video has three frames.  One
+    kernel forward, one backward (a gather per frame: no atomics, the same bits on every run)."""
+    return root_sm_parts(rtk_all, data_offset)[0]
+
+
+# flags of moda.py the assembly reads, with the reference's defaults (moda.py:53-172)
+LOSS_OPTS = dict(lineload=False, use_unc=False, img_size=512, warmup_steps=0.4, freeze_coarse=False, freeze_proj=False, proj_start=0.0,
+                 proj_end=0.2, ft_cse=False, mt_cse=True, use_embed=True, use_proj=True, use_corresp=True, total_wt=1.0, sil_wt=0.1,
+                 img_wt=0.1, feat_wt=0.0, use_corr=False, corr_wt=0.01, frnd_wt=1.0, proj_wt=0.02, flow_wt=1.0, cyc_wt=1.0,
+                 root_sm=True, eikonal_wt=0.0, bone_loc_reg=0.1, loss_flt=True, rm_novp=True, s3im_loss=False, s3im_wt=0.01,
+                 lbs=True, neudbs=True)
+
+
+def _opt(opts, name):
+    if isinstance(opts, dict):
+        return opts.get(name, LOSS_OPTS[name])
+    return getattr(opts, name, LOSS_OPTS[name])
+
+
+def proj_warmup_weight(progress, proj_start, proj_end):
+    """moda.py:633-635 in float64, as numpy evaluates it."""
+    w = (float(progress) - proj_start) / (proj_end - proj_start)
+    return float(np.clip((w - 0.8) * 5, 0, 1))
+
+
+def forward_loss(rendered, opts, *, loss_filter=None, errid=None, frameid=None, progress=0., loss_select=1, rtk_all=None,
+                 data_offset=None, extra_terms=()):
+    """The loss assembly of banmo.forward_default (moda.py:517-768) with the branches the reference's default flags take:
+    the frame filter (loss_flt: `loss_filter`, a LossFilter, with `errid` / `frameid`), rm_novp (five terms times the detached
+    rendered['sil_coarse']), root_sm (`rtk_all`, `data_offset`), the loss_select == 0 and projection warm-ups, total_wt.
+    Flags come from `opts` (an object or a dict), the reference's default (LOSS_OPTS) where one is absent.  The filter is three
+    launches, the root term one, the assembly ONE each way (moda_loss_assembly); nothing is read back, so the step can be captured.
+    -> (total_loss, aux_out): aux_out holds the reference's keys as 0-d device tensors, views of one output tensor.
+
+    Terms in the reference's order: img, sil, s3im, frnd, flo, feat, corr, proj (twice inside the warm-up window), cyc, elastic,
+    dis_reg, dis_reg_forward, root_sm, eikonal (rendered['eikonal_loss'], from `eikonal_loss`), vis, unc (`unc_loss`), then
+    `extra_terms` ((name, weight, tensor) each, added as weight * tensor.mean()); sixteen at the most.
+
+    Under graph capture: `progress`, `loss_select` and the projection warm-up weight are HOST values that decide which terms are
+    filtered and the carry / weight arguments of the launch -- a captured graph replays those of capture time.  Re-capture when
+    `progress` crosses warmup_steps, when loss_select changes, and do not capture inside (proj_start, proj_end) with freeze_proj,
+    where the weight changes every step.
+
+    Deviations, all stated: rendered['sil_loss_samp'] and rendered['flo_loss_samp'] are NOT zeroed in place at the rejected
+    rows (moda.py:536, :580) -- the zeroing happens inside the kernel and `rendered` is left as it was; bone_loc_reg (geomloss),
+    ft_cse and freeze_coarse raise NotImplementedError."""
+    o = lambda name: _opt(opts, name)
+    if (o("lbs") or o("neudbs")) and o("bone_loc_reg") > 0:
+        raise NotImplementedError("bone_loc_reg > 0 (the reference's default 0.1) needs geomloss' Sinkhorn divergence, which this "
+                                  "package does not implement: set opts.bone_loc_reg = 0")
+    if o("ft_cse") and o("mt_cse"):
+        raise NotImplementedError("ft_cse (the csenet fine-tuning term of moda.py:724-731) is not implemented")
+    if o("freeze_coarse"):
+        raise NotImplementedError("freeze_coarse (the xyz-weight terms of moda.py:733-755) is not implemented")
+    sil = rendered["sil_at_samp"]
+    invalid = None
+    if o("loss_flt"):                                                                  # moda.py:522-533
+        if loss_filter is None or errid is None:
+            raise ValueError("opts.loss_flt (the reference's default) needs loss_filter= (a LossFilter) and errid=")
+        weighted = rendered["sil_loss_samp"].detach() * o("sil_wt")
+        if loss_filter.lineload:
+            invalid = loss_filter(weighted, errid, frameid)
+        else:                                     # whole frames: errid has one entry per frame, the rays are bs equal runs (bs, n)
+            bs = errid.numel()
+            if bs < 1 or weighted.numel() % bs:
+                raise ValueError(f"forward_loss: {weighted.numel()} rays are not {bs} frames (errid) of equal length")
+            inv = loss_filter(weighted.reshape(bs, -1), errid)                         # (bs,) -> one flag per ray
+            invalid = inv[:, None].expand(bs, weighted.numel() // bs).reshape(-1)
+    scale = rendered["sil_coarse"] if o("rm_novp") else None
+    plan = []                                                                          # (aux key, x, weight, mask, kind, scale, drop, carry)
+
+    def add(key, x, wt, mask=None, kind=None, sc=None, drop=None, carry=1.0):
+        plan.append((key, x, wt, mask, kind, sc, drop, carry))
+
+    add("img_loss", rendered["img_loss_samp"], o("img_wt"), sil, ">0", scale, invalid)                           # :540-549
+    add("sil_loss", rendered["sil_loss_samp"], o("sil_wt"), rendered["vis_at_samp"], ">0", None,
+        invalid if progress > o("warmup_steps") else None)                                                        # :535-536, :550-551
+    if o("s3im_loss"):
+        add("s3im_loss", rendered["s3im_loss"], o("s3im_wt"))                                                    # :560-563
+    add("feat_rnd_loss", rendered["frnd_loss_samp"], o("frnd_wt"), sil, ">0", scale, invalid)                    # :566-574
+    if o("use_corresp"):                                                                                          # :577-594
+        add("flo_loss", rendered["flo_loss_samp"], 2.0 * o("flow_wt"), rendered["sil_at_samp_flo"], "bool", scale, invalid,
+            0.0 if loss_select == 0 else 1.0)
+    if o("use_embed"):                                                                                            # :597-618
+        add("feat_loss", rendered["feat_err"], o("feat_wt"), sil, ">0", scale, invalid)
+        if o("use_corr"):
+            add("corr_loss", rendered["corr_err"], o("corr_wt"), sil, ">0", scale, invalid)
+    if o("use_proj"):                                                                                             # :622-642
+        add("proj_loss", rendered["proj_err"], o("proj_wt"), sil, ">0", None, invalid)
+        if o("freeze_proj") and o("proj_start") < progress < o("proj_end"):
+            w = proj_warmup_weight(progress, o("proj_start"), o("proj_end"))
+            add(None, rendered["proj_err"], 10.0 * (1.0 - w) * o("proj_wt"), sil, ">0", None, invalid, w)      # total*w + 10*proj*(1-w)
+    if "frame_cyc_dis" in rendered:                                                                               # :645-656
+        add("cyc_loss", rendered["frame_cyc_dis"], o("cyc_wt"))
+        if "elastic_loss" in rendered:
+            add("elastic_loss", rendered["elastic_loss"], 1e-3)
+    if "dis_reg" in rendered:                                                                                     # :659-664
+        add(None, rendered["dis_reg"], 1.0)
+    if "dis_reg_forward" in rendered:
+        add(None, rendered["dis_reg_forward"], 1.0)
+    root_parts = None
+    if o("root_sm"):                                                                                              # :667-670
+        if rtk_all is None or data_offset is None:
+            raise ValueError("opts.root_sm (the reference's default) needs rtk_all= and data_offset=")
+        root, root_parts = root_sm_parts(rtk_all, data_offset)
+        add("root_sm_loss", root, 1.0)
+    if o("eikonal_wt") > 0:                                                                                       # :673-678
+        if "eikonal_loss" not in rendered:
+            raise KeyError("opts.eikonal_wt > 0: put moda_amd.loss_utils.eikonal_loss(...) into rendered['eikonal_loss']")
+        add("ekl_loss", rendered["eikonal_loss"], o("eikonal_wt"))
+    if "vis_loss" in rendered:                                                                                    # :701-704
+        add("visibility_loss", rendered["vis_loss"], 0.01)
+    if o("use_unc"):                                                                                              # :707-720
+        img = rendered["img_loss_samp"].detach() * o("img_wt")                                                   # :540
+        if invalid is not None:                                                                                   # :544 `*= 0`
+            img = img.reshape(invalid.numel(), -1) * (~invalid).to(img.dtype)[:, None]
+        add("unc_loss", unc_loss(rendered, img_loss_samp=img), 1.0)
+    for name, wt, x in extra_terms:
+        add(name, x, wt)
+    if len(plan) > 16:
+        raise ValueError(f"forward_loss: {len(plan)} terms, moda_loss_assembly takes 16")
+    spec = [(wt, mask, kind, sc, drop, carry) for _, _, wt, mask, kind, sc, drop, carry in plan]
+    total, rest = A.LossAssemblyFn.apply(spec, o("total_wt"), *[p[1] for p in plan])
+    T = len(plan)
+    aux_out = {}
+    for t, p in enumerate(plan):
+        if p[0] is not None:
+            aux_out[p[0]] = rest[2 * T + t] if p[0] == "cyc_loss" else rest[t]         # cyc_loss is logged unweighted (:650)
+    aux_out["total_loss"] = total.detach()
+    if root_parts is not None:
+        aux_out["root_rot_sm"], aux_out["root_trn_sm"] = root_parts[0], root_parts[1]
+    if invalid is not None:
+        aux_out["invalid"] = invalid
+        aux_out["filter_status"] = loss_filter.status
+    return total, aux_out
+
+
+def unc_loss(rendered, img_loss_samp=None):
     """The uncertainty network's own loss (moda.py:707-720): mean over rays of (sil_at_samp * img_loss_samp.mean(-1)).detach() -
-    unc_pred[..., 0], squared.  Only nerf_unc receives a gradient from it."""
-    target = (L.dev(rendered["sil_at_samp"])[..., 0] * rendered["img_loss_samp"].mean(-1)).detach()
+    unc_pred[..., 0], squared.  Only nerf_unc receives a gradient from it.  img_loss_samp: the tensor the reference has at that
+    point -- img_wt * rendered['img_loss_samp'] with the filter's rejected rows zeroed (moda.py:540-544; forward_loss passes it);
+    None: rendered['img_loss_samp'] as it is."""
+    img = rendered["img_loss_samp"] if img_loss_samp is None else img_loss_samp
+    sil0 = L.dev(rendered["sil_at_samp"])[..., 0]
+    target = (sil0 * img.reshape(tuple(sil0.shape) + (-1,)).mean(-1)).detach()
     return A.RowDistFn.apply(rendered["unc_pred"].reshape(-1, 1), target.reshape(-1, 1), True).mean()
 
 
