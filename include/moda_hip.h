@@ -905,6 +905,37 @@ typedef struct {
 } moda_asm_term;
 int moda_loss_assembly(const moda_asm_term* terms, int32_t n_terms, float total_wt, float* out, const float* g, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Debiased Sinkhorn divergence between two point clouds (moda_amd/csrc/sinkdiv_kernels.hip; additive entries of ABI 9: no
+ * existing signature changed): the bone-location term of nnutils/moda.py:693-695,
+ * SamplesLoss("sinkhorn", p=2, blur=.05)(x, y) of geomloss 0.2.4 with uniform weights, scaling given, reach None, debias True.
+ * geomloss is not part of the reference tree (misc/moda.yml:96 names the version): what follows restates its published
+ * sinkhorn_divergence.py, tensorized route, and is UNPINNED -- no reference binary or source checks it here.
+ *   max_diameter      d = |max(x u y) - min(x u y)|, the joint bounding box's diagonal (or `diameter` when > 0)
+ *   epsilon_schedule  eps_s = [d^2] + [exp(e) for e in arange(2 ln d, 2 ln blur, 2 ln scaling)] + [blur^2], n entries
+ *   softmin           softmin(eps, C, h)_r = -eps logsumexp_k(h_k - C_rk / eps), C(u, v) = |u - v|^2 / 2 from coordinate differences
+ *   sinkhorn_loop     initialisation at eps_s[0]; for every eps of eps_s one Jacobi update of a_x, b_y, a_y, b_x averaged with the
+ *                     old values; one last extrapolation at blur^2 without averaging
+ *   sinkhorn_cost     loss = mean_i (b_x - a_x)_i + mean_j (a_y - b_y)_j
+ *   gradient          what autograd returns through geomloss' detach pattern: the envelope gradient through the row point of the
+ *                     last extrapolation, grad_x_i = (1/N) [sum_j w_ij (x_i - y_j) - sum_k v_ik (x_i - x_k)], w / v the softmax
+ *                     weights of b_x's / a_x's last softmin; grad_y likewise (skipped when NULL).
+ * x (N,3), y (M,3) fp32 contiguous.  ws: moda_sinkdiv_ws_bytes(N, M) bytes, 4-byte aligned, no initialisation needed.  The
+ * schedule is decided ON THE DEVICE: 4 + MODA_SINKDIV_MAX_STEPS launches whatever the data, the step launches past n return after
+ * reading one word; nothing is read back, so the call may run on a capturing stream.  No float atomics: bit-identical from run
+ * to run.  status (4 int32) = [flags, n (0 when a flag is set), the bits of d as a float, 0].  A flag set: loss = NaN, the gradients zero.
+ * The coordinates are checked with `diameter` given too: a NaN or infinite one sets MODA_SINKDIV_BAD_DIAMETER.
+ * MODA_EINVAL: a NULL pointer (grad_y excepted), N < 1, M < 1, blur <= 0, scaling outside (0, 1).  MODA_ESHAPE: N + M >
+ * MODA_SINKDIV_MAX_POINTS (the joined cloud lives in one workgroup's LDS, 12 bytes a point).
+ * ------------------------------------------------------------------------ */
+#define MODA_SINKDIV_MAX_STEPS 24          /* n = 2 + ceil(log2(d / blur)) at scaling 0.5: d / blur <= 2^22 */
+#define MODA_SINKDIV_MAX_POINTS 4096
+#define MODA_SINKDIV_BAD_DIAMETER 1        /* a non-finite coordinate or d, or d <= blur: geomloss' arange is undefined or empty */
+#define MODA_SINKDIV_TOO_MANY_STEPS 2      /* n > MODA_SINKDIV_MAX_STEPS */
+int64_t moda_sinkdiv_ws_bytes(int64_t N, int64_t M);       /* 0 for a shape moda_sinkdiv refuses */
+int moda_sinkdiv(const float* x, const float* y, int64_t N, int64_t M, double blur, double scaling, double diameter, void* ws,
+                 float* loss_out, float* grad_x, float* grad_y, int32_t* status, void* stream);
+
 /* S3IM, opts.s3im_loss (nnutils/loss_utils.py:575-702 S3IM.forward + SSIM(window 4, stride 4) / _ssim; called at
  * nnutils/rendering.py:528-532):  loss[0] = 1 - mean SSIM over the Gaussian 4x4 / stride 4 / padding 1 windows of the
  * (3, patch_h, patch_w_total) virtual patch whose pixel (h, w) holds row index[h * patch_w_total + w] % N of rgb * mask and of

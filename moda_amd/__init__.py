@@ -30,3 +30,6 @@ from . import overflow  # noqa: F401
 from .autograd import set_train_precision, get_train_precision, GradBucket  # noqa: F401
 from . import train_utils  # noqa: F401
 from .train_utils import GradClipper, clip_grad, grad_group, GRAD_GROUPS  # noqa: F401
+from . import samples_loss  # noqa: F401
+from .samples_loss import SamplesLoss  # noqa: F401
+from .loss_utils import bone_loc_loss  # noqa: F401

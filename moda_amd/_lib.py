@@ -153,6 +153,9 @@ _SIGNATURES = {
     "moda_loss_filter_frame": (_c.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _P, _I32, _c.c_double, _P, _P, _P, _P]),
     "moda_root_sm": (_c.c_int, [_P, _I32, _I64, _P, _I32, _P, _P, _P, _P]),
     "moda_loss_assembly": (_c.c_int, [_P, _I32, _F32, _P, _P, _P]),
+    # debiased Sinkhorn divergence of two point clouds (sinkdiv_kernels.hip): additive entries of ABI 9
+    "moda_sinkdiv_ws_bytes": (_I64, [_I64, _I64]),
+    "moda_sinkdiv": (_c.c_int, [_P, _P, _I64, _I64, _c.c_double, _c.c_double, _c.c_double, _P, _P, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

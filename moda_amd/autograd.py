@@ -10,6 +10,7 @@ import os
 
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 
@@ -1344,3 +1345,34 @@ class ExpandRowsFn(Function):
         out = torch.empty((g2.shape[0] // ctx.k, C), device=g2.device, dtype=torch.float32)
         L.call("moda_segsum_f32", L.ptr(g2), out.shape[0], ctx.k, C, C, L.ptr(out), C, L.stream())
         return out, None
+
+
+class SinkhornDivFn(Function):
+    """geomloss' debiased Sinkhorn divergence between x (N,3) and y (M,3), uniform weights (moda_sinkdiv; include/moda_hip.h
+    names the geomloss functions it restates).  The forward is ONE call: it leaves the value and, from the same last pass, the
+    gradients geomloss' autograd would return; the backward scales them by the upstream gradient -- no second solve.
+    `diameter` None or <= 0: the joint bounding box, reduced on the device.  status (4,) int32 is written by the call.
+    -> the divergence, a 0-dim tensor."""
+
+    @staticmethod
+    def forward(ctx, x, y, blur, scaling, diameter, status):
+        xs, ys = _f32(x), _f32(y)
+        N, M = xs.shape[0], ys.shape[0]
+        nbytes = L.load().moda_sinkdiv_ws_bytes(N, M)
+        if nbytes <= 0:
+            raise ValueError(f"moda_sinkdiv: N + M = {N + M} points, the kernels hold at most 4096 (MODA_ESHAPE)")
+        ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=xs.device)
+        loss = torch.empty((1,), device=xs.device)
+        gx = torch.empty_like(xs)
+        need_y = ctx.needs_input_grad[1]
+        gy = torch.empty_like(ys) if need_y else None
+        L.call("moda_sinkdiv", L.ptr(xs), L.ptr(ys), N, M, float(blur), float(scaling), float(diameter or 0.0), L.ptr(ws), L.ptr(loss),
+               L.ptr(gx), L.ptr(gy), L.ptr(status), L.stream())
+        ctx.save_for_backward(gx, gy)
+        return loss.reshape(())
+
+    @staticmethod
+    @once_differentiable                 # the kept gradients are constants: a second derivative through them is an error, not 0
+    def backward(ctx, g):
+        gx, gy = ctx.saved_tensors
+        return (gx * g if ctx.needs_input_grad[0] else None), (gy * g if gy is not None else None), None, None, None, None

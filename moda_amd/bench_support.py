@@ -83,7 +83,7 @@ class TrainHarness:
 
     def __init__(self, N=2048, S=128, B=25, precision="bf16", rank=0, world=1, dist=None, lr=2e-5, device=None, seed=1000,
                  rays_per_frame=4, fused_adamw=True, bucket=True, use_fine=False, with_unc=False, strong=False, clip_grad=False,
-                 clip_scale=10.0, default_losses=False):
+                 clip_scale=10.0, default_losses=False, bone_loc=False):
         """use_fine / with_unc: the reference's LAST training stage (scripts/template.sh:59: --fine_steps 0 --use_unc): S/2 coarse
         depths rendered without gradients (rendering.py:91-107, here on the fused inference kernels in `PREPASS_PRECISION[precision]`),
         S/2 importance samples merged in, and the uncertainty network nerf_unc (8x256, moda.py:457-464) trained on
@@ -94,7 +94,12 @@ class TrainHarness:
         default_losses: assemble the loss as the reference's default flags do (moda.py:167-168 loss_flt, rm_novp) through
         moda_amd.loss_utils.forward_loss with a device-resident LossFilter in line mode: ray i belongs to frame
         i // rays_per_frame and to line i % rays_per_frame of it.  root_sm stays off (the synthetic scene has no camera table).
-        Off by default: the default path and the benchmarked step are unchanged."""
+        Off by default: the default path and the benchmarked step are unchanged.
+        bone_loc (with default_losses): the bone-location term of moda.py:681-698 at the reference's bone_loc_reg = 0.1 inside the
+        step -- the Sinkhorn divergence (moda_amd.samples_loss) between this harness's bone centres `bones_rst[:, :3] * 10` and
+        1000 points drawn on a fixed synthetic rest mesh (synth.make_rest_mesh) from the preallocated uniforms `bone_u`, which
+        draw() refills: replay and eager see the same samples.  The synthetic scene has no rest-pose head, so correct_bones is
+        not part of it.  Off by default."""
         from moda_amd import sharding
         global DEV
         # strong=True: ONE batch of N rays (the one-rank run's rays) cut into contiguous per-rank ranges (sharding.shard_rays), so
@@ -185,9 +190,22 @@ class TrainHarness:
             self.frameid = (idx // rays_per_frame).to(torch.int32)
             self.errid = self.frameid * 512 + (idx % rays_per_frame).to(torch.int32)
             w = TRAIN_WEIGHTS
-            self.loss_opts = dict(loss_flt=True, rm_novp=True, root_sm=False, bone_loc_reg=0.0, lineload=True, use_unc=self.with_unc,
+            self.loss_opts = dict(loss_flt=True, rm_novp=True, root_sm=False, bone_loc_reg=0.1 if bone_loc else 0.0, lineload=True,
+                                  use_unc=self.with_unc,
                                   img_wt=w["img_wt"], sil_wt=w["sil_wt"], frnd_wt=w["frnd_wt"], flow_wt=w["flow_wt"],
                                   feat_wt=w["feat_wt"], proj_wt=w["proj_wt"], cyc_wt=w["cyc_wt"])
+
+        self.bone_loc = bool(bone_loc)
+        if self.bone_loc:
+            if not self.default_losses:
+                raise ValueError("TrainHarness: bone_loc=True is a term of the default loss assembly (default_losses=True)")
+            from moda_amd.mesh import TriMesh
+            from moda_amd.samples_loss import SamplesLoss
+            v, f = synth.make_rest_mesh()
+            self.mesh_rest = TriMesh(torch.from_numpy(v).to(self.dev), torch.from_numpy(f).to(self.dev))
+            self.bone_u = torch.empty((1000, 3), device=self.dev)       # uniforms of sample_points_from_meshes
+            self.samples_loss = SamplesLoss("sinkhorn", p=2, blur=.05)
+            self.bone_loc_value = None                                   # the unweighted term of the last step
 
     def named_params(self):
         """`self.params` under the names the reference's model gives them (what clip_grad groups by): the networks by their
@@ -218,6 +236,8 @@ class TrainHarness:
         self.feat_noise.normal_(generator=self.gen)
         if self.pdf_u is not None:
             self.pdf_u.uniform_(generator=self.gen)
+        if self.bone_loc:
+            self.bone_u.uniform_(generator=self.gen)
 
     def fwd_bwd(self):
         from moda_amd.loss_utils import total_loss, unc_loss
@@ -243,7 +263,15 @@ class TrainHarness:
         `progress` is 1 (past warmup_steps: the silhouette term is filtered too); the visibility term carries the reference's
         0.01 (moda.py:702), not TRAIN_WEIGHTS' vis_wt.  `terms` keeps TRAIN_TERMS' order; its cycle entry is weighted."""
         from moda_amd.loss_utils import forward_loss
-        loss, aux = forward_loss(r, self.loss_opts, loss_filter=self.loss_filter, errid=self.errid, frameid=self.frameid, progress=1.0)
+        bone_loc = None
+        if self.bone_loc:                                              # moda.py:690-695 (no rest-pose head in the synthetic scene)
+            samp = moda_amd.sample_points_from_meshes(self.mesh_rest, u=self.bone_u)
+            bone_loc = self.samples_loss(self.models["bones_rst"][:, :3] * 10, samp * 10)
+            # detached: a tensor kept WITH its graph would keep the bones' gradient-accumulation node of this call alive, and that
+            # node runs on the stream of the call that created it -- inside a later capture, on a stream that is not capturing
+            self.bone_loc_value = bone_loc.detach()
+        loss, aux = forward_loss(r, self.loss_opts, loss_filter=self.loss_filter, errid=self.errid, frameid=self.frameid, progress=1.0,
+                                 bone_loc=bone_loc)
         loss.backward()
         keys = ("img_loss", "sil_loss", "feat_rnd_loss", "flo_loss", "feat_loss", "proj_loss", "visibility_loss", "cyc_loss")
         self.terms.copy_(torch.stack([aux[k] for k in keys]))

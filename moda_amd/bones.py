@@ -191,16 +191,19 @@ def _sample_one(verts, faces, u, what):
         raise ValueError(f"{what}: {S} samples exceed int32 indices")
     dev = verts.device
     areas, cdf, n_bad = face_cdf(verts, faces)
-    chk = torch.stack([torch.isfinite(verts).all().double(), n_bad[0].double(), cdf[-1],
-                       ((u >= 0) & (u < 1)).all().double()]).cpu()          # the one read-back
-    if not chk[0]:
-        raise ValueError(f"{what}: non-finite vertex coordinate")
-    if chk[1]:
-        raise ValueError(f"{what}: {int(chk[1])} face(s) index a vertex outside [0, {V})")
-    if not chk[2] > 0:
-        raise ValueError(f"{what}: the mesh has total area {float(chk[2])}")
-    if not chk[3]:
-        raise ValueError(f"{what}: u outside [0, 1)")
+    if not torch.cuda.is_current_stream_capturing():
+        chk = torch.stack([torch.isfinite(verts).all().double(), n_bad[0].double(), cdf[-1],
+                           ((u >= 0) & (u < 1)).all().double()]).cpu()          # the one read-back
+        if not chk[0]:
+            raise ValueError(f"{what}: non-finite vertex coordinate")
+        if chk[1]:
+            raise ValueError(f"{what}: {int(chk[1])} face(s) index a vertex outside [0, {V})")
+        if not chk[2] > 0:
+            raise ValueError(f"{what}: the mesh has total area {float(chk[2])}")
+        if not chk[3]:
+            raise ValueError(f"{what}: u outside [0, 1)")
+    # (while a graph is being captured nothing may be read back: the checks above are those of the eager warm-up calls; the
+    # kernels themselves skip a face with an index outside [0, V) and clamp the face search, so a replay reads nothing out of bounds)
     points = torch.empty((S, 3), dtype=torch.float32, device=dev)
     face = torch.empty(S, dtype=torch.int32, device=dev)
     L.call("moda_mesh_sample", L.ptr(verts), L.ptr(faces), V, F, L.ptr(areas), L.ptr(cdf), L.ptr(u), S, L.ptr(points), L.ptr(face),
@@ -214,7 +217,8 @@ def sample_points_from_meshes(verts, faces=None, num_samples=10000, return_norma
     `Meshes` (moda.py:687-691) pass the mesh, or its tensors, directly: -> points (S,3), or (B,S,3) for (B,V,3) / (B,F,3) input.
     Faces are drawn in proportion to their area and points uniformly inside them, pytorch3d's published construction (see
     `sample_surface`).  The uniforms are `u` ((S,3) shared by the batch, or (B,S,3)) when given, else torch.rand on the device
-    with `generator`; the draw itself is a pure function of them."""
+    with `generator`; the draw itself is a pure function of them.  While a graph is being captured the mesh / `u` validation
+    (one read-back) is skipped: the eager warm-up calls make it; the kernels skip bad faces and clamp the face search."""
     if return_normals:
         raise NotImplementedError("sample_points_from_meshes: return_normals=True is not implemented")
     what = "sample_points_from_meshes"

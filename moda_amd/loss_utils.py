@@ -462,8 +462,38 @@ def proj_warmup_weight(progress, proj_start, proj_end):
     return float(np.clip((w - 0.8) * 5, 0, 1))
 
 
+def bone_loc_loss(model, mesh_rest, opts=None, *, num_samples=1000, generator=None, u=None, samples_loss=None):
+    """The bone-location term of moda.py:681-698, unweighted: the rest bones moved by the rest pose (correct_bones), `num_samples`
+    points drawn on the rest mesh (sample_points_from_meshes; `generator` / `u` as there), and the debiased Sinkhorn divergence
+    SamplesLoss("sinkhorn", p=2, blur=.05) between the bone centres and the samples, both times 10 (moda_amd.samples_loss).
+    -> a 0-dim tensor to pass as forward_loss(..., bone_loc=); None when the mesh has 100 vertices or fewer, the reference's
+    silent skip (moda.py:686: a shape test, nothing is read back) -- pass bone_loc=False then.
+    Gradient reaches model.bones, rest_pose_code and the pose head through correct_bones' autograd; none flows to the samples.
+    mesh_rest: a TriMesh or anything with .vertices / .faces.  samples_loss: a SamplesLoss("sinkhorn", p=2, blur=.05) to reuse --
+    its .status tensor then tells why a term came out NaN (a non-finite bone or sample, a degenerate diameter); None builds one."""
+    from .bones import sample_points_from_meshes
+    from .feeders import correct_bones
+    from .samples_loss import SamplesLoss
+    verts = getattr(mesh_rest, "vertices_t", None)
+    if verts is None:
+        verts = mesh_rest.vertices
+    if len(verts) <= 100:                                                              # moda.py:686
+        return None
+    bones_rst, _ = correct_bones(model, model.bones, neudbs=True if opts is None else _opt(opts, "neudbs"))   # moda.py:683-684
+    if torch.is_tensor(verts) and hasattr(mesh_rest, "faces_t"):
+        samp = sample_points_from_meshes(mesh_rest, num_samples=num_samples, generator=generator, u=u)
+    else:
+        dev = bones_rst.device
+        v = torch.as_tensor(np.asarray(mesh_rest.vertices), dtype=torch.float32).to(dev)
+        f = torch.as_tensor(np.asarray(mesh_rest.faces).astype(np.int32)).to(dev)
+        samp = sample_points_from_meshes(v, f, num_samples=num_samples, generator=generator, u=u)
+    if samples_loss is None:
+        samples_loss = SamplesLoss("sinkhorn", p=2, blur=.05)
+    return samples_loss(bones_rst[:, :3] * 10, samp.detach() * 10)                                  # moda.py:693-695
+
+
 def forward_loss(rendered, opts, *, loss_filter=None, errid=None, frameid=None, progress=0., loss_select=1, rtk_all=None,
-                 data_offset=None, extra_terms=()):
+                 data_offset=None, extra_terms=(), bone_loc=None):
     """The loss assembly of banmo.forward_default (moda.py:517-768) with the branches the reference's default flags take:
     the frame filter (loss_flt: `loss_filter`, a LossFilter, with `errid` / `frameid`), rm_novp (five terms times the detached
     rendered['sil_coarse']), root_sm (`rtk_all`, `data_offset`), the loss_select == 0 and projection warm-ups, total_wt.
@@ -472,8 +502,14 @@ def forward_loss(rendered, opts, *, loss_filter=None, errid=None, frameid=None, 
     -> (total_loss, aux_out): aux_out holds the reference's keys as 0-d device tensors, views of one output tensor.
 
     Terms in the reference's order: img, sil, s3im, frnd, flo, feat, corr, proj (twice inside the warm-up window), cyc, elastic,
-    dis_reg, dis_reg_forward, root_sm, eikonal (rendered['eikonal_loss'], from `eikonal_loss`), vis, unc (`unc_loss`), then
-    `extra_terms` ((name, weight, tensor) each, added as weight * tensor.mean()); sixteen at the most.
+    dis_reg, dis_reg_forward, root_sm, eikonal (rendered['eikonal_loss'], from `eikonal_loss`), bone_loc, vis, unc (`unc_loss`),
+    then `extra_terms` ((name, weight, tensor) each, added as weight * tensor.mean()); sixteen at the most.
+
+    bone_loc (moda.py:681-698, with lbs / neudbs and bone_loc_reg > 0, the reference's default 0.1): pass
+    `bone_loc=bone_loc_loss(model, mesh_rest)`, a 0-dim tensor -- the term bone_loc_reg * bone_loc is added and logged as
+    aux_out['bone_loc_loss'] (weighted, as the reference logs it).  bone_loc_loss returns None for a rest mesh of 100 vertices or
+    fewer, where the reference skips the term silently: pass `bone_loc=False` for that skip.  bone_loc=None with the flag on
+    raises -- a forgotten term must not pass for the reference's skip.
 
     Under graph capture: `progress`, `loss_select` and the projection warm-up weight are HOST values that decide which terms are
     filtered and the carry / weight arguments of the launch -- a captured graph replays those of capture time.  Re-capture when
@@ -481,12 +517,16 @@ def forward_loss(rendered, opts, *, loss_filter=None, errid=None, frameid=None, 
     where the weight changes every step.
 
     Deviations, all stated: rendered['sil_loss_samp'] and rendered['flo_loss_samp'] are NOT zeroed in place at the rejected
-    rows (moda.py:536, :580) -- the zeroing happens inside the kernel and `rendered` is left as it was; bone_loc_reg (geomloss),
-    ft_cse and freeze_coarse raise NotImplementedError."""
+    rows (moda.py:536, :580) -- the zeroing happens inside the kernel and `rendered` is left as it was; the bone-location term is computed by the caller
+    (bone_loc_loss: it needs the model and the rest mesh, which `rendered` does not hold) and its Sinkhorn divergence restates
+    geomloss 0.2.4, which the reference tree does not contain; ft_cse and freeze_coarse raise NotImplementedError."""
     o = lambda name: _opt(opts, name)
-    if (o("lbs") or o("neudbs")) and o("bone_loc_reg") > 0:
-        raise NotImplementedError("bone_loc_reg > 0 (the reference's default 0.1) needs geomloss' Sinkhorn divergence, which this "
-                                  "package does not implement: set opts.bone_loc_reg = 0")
+    with_bone_loc = (o("lbs") or o("neudbs")) and o("bone_loc_reg") > 0
+    if with_bone_loc and bone_loc is None:
+        raise NotImplementedError("bone_loc_reg > 0 (the reference's default 0.1) needs the bone-location term: pass bone_loc="
+                                  "moda_amd.loss_utils.bone_loc_loss(model, mesh_rest) (a 0-dim tensor), bone_loc=False where that "
+                                  "returns None (a rest mesh of 100 vertices or fewer: the reference's skip), or set "
+                                  "opts.bone_loc_reg = 0")
     if o("ft_cse") and o("mt_cse"):
         raise NotImplementedError("ft_cse (the csenet fine-tuning term of moda.py:724-731) is not implemented")
     if o("freeze_coarse"):
@@ -547,6 +587,10 @@ def forward_loss(rendered, opts, *, loss_filter=None, errid=None, frameid=None, 
         if "eikonal_loss" not in rendered:
             raise KeyError("opts.eikonal_wt > 0: put moda_amd.loss_utils.eikonal_loss(...) into rendered['eikonal_loss']")
         add("ekl_loss", rendered["eikonal_loss"], o("eikonal_wt"))
+    if with_bone_loc and bone_loc is not False:                                                                   # :681-698
+        if not (torch.is_tensor(bone_loc) and bone_loc.numel() == 1):
+            raise ValueError("forward_loss: bone_loc must be the 0-dim tensor of bone_loc_loss(...), or False")
+        add("bone_loc_loss", bone_loc, o("bone_loc_reg"))
     if "vis_loss" in rendered:                                                                                    # :701-704
         add("visibility_loss", rendered["vis_loss"], 0.01)
     if o("use_unc"):                                                                                              # :707-720

@@ -121,6 +121,31 @@ def make_bones(seed, B):
     return bones
 
 
+def make_rest_mesh(subdivisions=2, radius=(0.3, 0.2, 0.25)):
+    """A fixed rest mesh for the bone-location term: an icosphere (10 * 4^subdivisions + 2 vertices: 162 at 2) squashed to the
+    semi-axes `radius`, around the bones of make_bones.  -> (vertices (V,3) float32, faces (F,3) int32)."""
+    t = (1.0 + np.sqrt(5.0)) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1),
+         (-t, 0, -1), (-t, 0, 1)]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    v = [np.asarray(p, np.float64) / np.linalg.norm(p) for p in v]
+    for _ in range(subdivisions):
+        mids, nf = {}, []
+        for tri in f:
+            m = []
+            for a, b in ((tri[0], tri[1]), (tri[1], tri[2]), (tri[2], tri[0])):
+                key = (min(a, b), max(a, b))
+                if key not in mids:
+                    q = v[a] + v[b]
+                    v.append(q / np.linalg.norm(q))
+                    mids[key] = len(v) - 1
+                m.append(mids[key])
+            nf += [(tri[0], m[0], m[2]), (tri[1], m[1], m[0]), (tri[2], m[2], m[1]), (m[0], m[1], m[2])]
+        f = nf
+    return (np.asarray(v) * np.asarray(radius)).astype(np.float32), np.asarray(f, np.int32)
+
+
 def make_models(seed, B=25, with_skin=True, with_feat=False, with_vis=False, with_app=False, beta=0.1,
                 perturb_bones=False, with_dis=False):
     """Parameter sets of the `models` dict moda.__init__ builds (moda.py:271-348,444-449), as numpy dicts."""
