@@ -29,7 +29,7 @@ extern "C" {
 #define MODA_EINVAL (-1)   /* unsupported / inconsistent argument */
 #define MODA_ESHAPE (-2)   /* shape outside what the kernels were instantiated for */
 
-/* ABI version; bumped on any signature change. */
+/* ABI version; bumped on any signature change.  10: the two older loss-sum entries left (both are moda_loss_assembly). */
 int moda_abi_version(void);
 
 /* 0 when `stream` is not being captured into a HIP graph, else the runtime's id of that capture (hipStreamGetCaptureInfo): a
@@ -819,36 +819,12 @@ int moda_ray_loss(const float* rgb, const float* sil, const float* flo, const fl
                   const float* g_img, const float* g_sil, const float* g_flo, float* d_rgb, float* d_sil, float* d_flo,
                   void* stream);
 
-/* x[mask].mean() as a trainer's loss assembly forms it (nnutils/moda.py:540-640), without the boolean gather (no host sync):
- * out2[0] = sum_i sum_c x[i, c] [mask_i != 0] / out2[1], out2[1] = k * #selected; x (N, k), mask (N).  Backward when dx is given:
- * dx[i, c] = g[0] [mask_i != 0] / out2[1]. */
-int moda_masked_mean(const float* x, const float* mask, int64_t N, int32_t k, float* out2, const float* g, float* dx,
-                     void* stream);
-
 /* Per-row distance of two (N, F) arrays -- the small reductions of the loss heads: mean_sq == 0: out[i] = ||a_i - b_i||_2
  * (feat_err nnutils/loss_utils.py:200, the reprojection error :216-221); mean_sq != 0: out[i] = mean_c (a_ic - b_ic)^2 (the
  * rendered-feature error, nnutils/rendering.py:573-577).  g == NULL: forward.  g (N) != NULL: backward -- da and / or db (N, F)
  * written: da = g (a - b) / ||a - b|| (0 where the norm is 0) or g 2 (a - b) / F; db = -da. */
 int moda_row_dist(const float* a, const float* b, int64_t N, int32_t F, int32_t mean_sq, float* out, const float* g, float* da,
                   float* db, void* stream);
-
-/* The weighted sum of a trainer's loss terms (nnutils/moda.py:540-705: `w * x[mask].mean()` per term, summed) in one launch each
- * way.  Term t: x (n, k) values; mask NULL / mask_kind 0 = every row, 1 = float (n), selected where > 0, 2 = uint8 / bool (n),
- * selected where != 0, 3 = float, selected where != 0; weight.  `terms` is a HOST array of n_terms <= 16 entries.
- * g == NULL, forward: out[0] = sum_t term_t, out[1 + t] = term_t = weight_t * sum(selected x) / den_t, out[1 + n_terms + t] =
- * den_t = k_t * #selected (a term with nothing selected is NaN, the mean of an empty selection there).
- * g != NULL, backward: for every term with dx != NULL, dx (n, k) = g[0] * weight_t / den_t on the selected rows, 0 elsewhere
- * (`out` as the forward call left it; x may be NULL). */
-typedef struct {
-    const float* x;
-    const void* mask;
-    float* dx;
-    int64_t n;
-    int32_t k, mask_kind;
-    float weight;
-    int32_t reserved;
-} moda_loss_term;
-int moda_loss_terms(const moda_loss_term* terms, int32_t n_terms, float* out, const float* g, void* stream);
 
 /* ---- the loss stage with the reference's default flags (loss_flt, rm_novp, root_sm; lossasm_kernels.hip): additive entries of
  * ABI 9.  Nothing here allocates or synchronises; every launch goes to `stream`, so the calls can be captured into a graph. ---- */
@@ -885,14 +861,18 @@ int moda_loss_filter_frame(const float* x, const void* mask, int32_t mask_u8, in
 int moda_root_sm(const float* rtk, int32_t rows, int64_t T, const int32_t* offsets, int32_t n_videos, float* out4, const float* g,
                  float* drtk, void* stream);
 
-/* The loss assembly of banmo.forward_default with every branch (nnutils/moda.py:517-768).  Term t: the rows of x (n, k) selected
- * by mask (kinds as moda_loss_term), each element multiplied by keep = (drop[row] ? 0 : 1) and then by scale[row] (either may be
- * NULL: no product) -- products, so a NaN in a dropped row stays NaN; mean_t = sum / (k * #selected), dropped rows counted.
- * total <- carry_t * total + weight_t * mean_t in term order from 0, then total * total_wt.  `terms` is a HOST array, <= 16.
+/* The loss assembly of banmo.forward_default with every branch (nnutils/moda.py:517-768): `w * x[mask].mean()` per term, summed.
+ * Term t: the rows of x (n, k) selected by mask -- mask NULL / mask_kind 0 = every row, 1 = float (n), selected where > 0, 2 =
+ * uint8 / bool (n), selected where != 0, 3 = float (n), selected where != 0 -- each element multiplied by keep = (drop[row] ? 0 : 1)
+ * and then by scale[row] (either may be NULL: no product) -- products, so a NaN in a dropped row stays NaN, while an unselected
+ * row is not read into the sum at all; mean_t = sum / (k * #selected), dropped rows counted (nothing selected: NaN, the mean of
+ * an empty selection).  total <- carry_t * total + weight_t * mean_t in term order from 0, then total * total_wt.  `terms` is a
+ * HOST array, <= 16.
  * g == NULL, forward: out (1 + 3 n_terms) = [total, weight_t * mean_t ..., den_t ..., mean_t ...].
  * g != NULL, backward: dx_t (n, k) = g[0] * total_wt * weight_t * prod_{s > t} carry_s / den_t * scale * keep on the selected rows,
- * 0 elsewhere, for every term with dx != NULL (x may be NULL); nothing flows into scale.  One launch each way.  Without scale,
- * drop, carry != 1 and total_wt != 1 the values are moda_loss_terms' bit for bit. */
+ * 0 elsewhere, for every term with dx != NULL (x may be NULL; `out` as the forward call left it); nothing flows into scale.  One
+ * launch each way.  The plain weighted sum of masked means (no scale, no drop, carry = total_wt = 1) and a single masked mean are
+ * calls of this entry: until ABI 9 each had an entry and a kernel pair of its own; the former's bits are reproduced. */
 typedef struct {
     const float* x;
     const void* mask;

@@ -24,11 +24,6 @@ class GemmDesc(_c.Structure):
                 ("mask_bits", _P), ("ld_bits", _I64)]
 
 
-class LossTerm(_c.Structure):       # moda_hip.h moda_loss_term
-    _fields_ = [("x", _P), ("mask", _P), ("dx", _P), ("n", _I64), ("k", _I32), ("mask_kind", _I32), ("weight", _F32),
-                ("reserved", _I32)]
-
-
 class AsmTerm(_c.Structure):        # moda_hip.h moda_asm_term
     _fields_ = [("x", _P), ("mask", _P), ("scale", _P), ("drop", _P), ("dx", _P), ("n", _I64), ("k", _I32), ("mask_kind", _I32),
                 ("weight", _F32), ("carry", _F32)]
@@ -118,8 +113,6 @@ _SIGNATURES = {
     "moda_match_ecols": (_c.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _F32, _P, _I32, _P]),
     "moda_match_dbar": (_c.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _I64, _I64, _P, _P, _P, _I32, _P]),
     "moda_ray_loss": (_c.c_int, [_P] * 9 + [_I64, _I32] + [_P] * 11 + [_P]),
-    "moda_masked_mean": (_c.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P]),
-    "moda_loss_terms": (_c.c_int, [_P, _I32, _P, _P, _P]),
     "moda_row_dist": (_c.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     "moda_dbg_poison_lds": (_c.c_int, [_c.c_uint32, _P]),
     "moda_fold_final": (_c.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P]),
@@ -159,7 +152,7 @@ _SIGNATURES = {
 }
 
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 9        # moda_abi_version() of the library these signatures describe (include/moda_hip.h)
+ABI_VERSION = 10       # moda_abi_version() of the library these signatures describe (include/moda_hip.h)
 _lib = None
 
 

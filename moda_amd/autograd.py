@@ -709,31 +709,6 @@ class RayLossFn(Function):
         return d_rgb.view(sh[0]), d_sil.view(sh[1]), d_flo.view(sh[2]), None, None, None, None, None, None, None
 
 
-class MaskedMeanFn(Function):
-    """x[mask].mean() without the boolean gather: x (N, k) or (N,), mask (N, 1) / (N,) (non-zero = selected) -> 0-dim."""
-
-    @staticmethod
-    def forward(ctx, x, mask):
-        x2 = _f32(x)
-        N = x2.shape[0]
-        x2 = x2.reshape(N, -1)
-        m = mask.reshape(N).to(torch.float32).contiguous()
-        out = torch.empty((2,), device=x2.device)
-        L.call("moda_masked_mean", L.ptr(x2), L.ptr(m), N, x2.shape[1], L.ptr(out), None, None, L.stream())
-        ctx.save_for_backward(m, out)
-        ctx.shape = x.shape
-        ctx.k = x2.shape[1]
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        m, out = ctx.saved_tensors
-        N = m.shape[0]
-        dx = torch.empty((N, ctx.k), device=m.device)
-        L.call("moda_masked_mean", None, L.ptr(m), N, ctx.k, L.ptr(out), L.ptr(_f32(g).reshape(1)), L.ptr(dx), L.stream())
-        return dx.view(ctx.shape), None
-
-
 class RowDistFn(Function):
     """Per-row distance of a and b (..., F): ||a - b||_2 (loss_utils.py:200, :216-221) or, mean_sq=True, mean_c (a - b)^2
     (rendering.py:573-577) -> (...,).  One kernel each way (moda_row_dist) where the eager form is 3 + ~9 launches."""
@@ -765,63 +740,13 @@ class RowDistFn(Function):
         return (None if da is None else da.view(sa)), (None if db is None else db.view(sb)), None
 
 
-class LossTermsFn(Function):
-    """sum_t w_t * x_t[mask_t].mean() of a trainer's loss assembly (moda.py:540-705) as one launch each way (moda_loss_terms).
-    spec: one (weight, mask, kind) per value tensor -- mask None (every row), or an (n,) / (n, 1) tensor: float selected where
-    > 0 (kind '>0'), bool (kind 'bool').  -> (total 0-dim, terms (T,) detached weighted terms)."""
-
-    @staticmethod
-    def forward(ctx, spec, *xs):
-        T = len(xs)
-        dev = xs[0].device
-        out = torch.empty((1 + 2 * T,), device=dev)
-        arr = (L.LossTerm * T)()
-        keep = []
-        for t, (x, (w, mask, kind)) in enumerate(zip(xs, spec)):
-            x2 = _f32(x)
-            n = x2.shape[0] if x2.dim() > 0 else 1
-            x2 = x2.reshape(n, -1)
-            mk, mp = 0, None
-            if mask is not None:
-                if kind == "bool":
-                    m = mask.reshape(-1).contiguous()
-                    if m.dtype != torch.bool:
-                        raise TypeError("kind 'bool' needs a bool mask")
-                    mk = 2
-                else:
-                    m = _f32(mask).reshape(-1)
-                    mk = 1
-                if m.numel() != n:
-                    raise ValueError(f"term {t}: {n} rows but a mask of {m.numel()}")
-                mp = L.ptr(m)
-                keep.append(m)
-            keep.append(x2)
-            arr[t] = L.LossTerm(x=L.ptr(x2), mask=mp, dx=None, n=n, k=x2.shape[1], mask_kind=mk, weight=float(w), reserved=0)
-        L.call("moda_loss_terms", arr, T, L.ptr(out), None, L.stream())
-        ctx.arr, ctx.keep, ctx.shapes, ctx.T = arr, keep, [tuple(x.shape) for x in xs], T
-        ctx.save_for_backward(out)
-        total, terms = out[0], out[1:1 + T]
-        ctx.mark_non_differentiable(terms)
-        return total, terms
-
-    @staticmethod
-    def backward(ctx, g, _g_terms):
-        out, = ctx.saved_tensors
-        dxs = []
-        for t in range(ctx.T):
-            need = ctx.needs_input_grad[1 + t]
-            dx = torch.empty((ctx.arr[t].n, ctx.arr[t].k), device=out.device) if need else None
-            ctx.arr[t].dx = L.ptr(dx)
-            dxs.append(dx)
-        L.call("moda_loss_terms", ctx.arr, ctx.T, L.ptr(out), L.ptr(_f32(g).reshape(1)), L.stream())
-        return (None,) + tuple(None if d is None else d.view(sh) for d, sh in zip(dxs, ctx.shapes))
-
-
 class LossAssemblyFn(Function):
-    """The loss assembly of moda.py:517-768 with its filter, rm_novp and warm-up branches, one launch each way
-    (moda_loss_assembly): total <- carry_t * total + weight_t * mean_t in term order, times total_wt.
-    spec: one (weight, mask, kind, scale, drop, carry) per value tensor -- mask / kind as LossTermsFn; scale None or a float
-    tensor with one entry per row (taken detached: nothing flows into it); drop None or a bool / uint8 tensor per row.
+    """sum_t w_t * x_t[mask_t].mean() of a trainer's loss assembly (moda.py:517-768) with its filter, rm_novp and warm-up
+    branches, one launch each way (moda_loss_assembly): total <- carry_t * total + weight_t * mean_t in term order, times
+    total_wt.  The one entry behind loss_utils.forward_loss, total_loss and masked_mean.
+    spec: one (weight, mask, kind, scale, drop, carry) per value tensor -- mask None (every row), or a tensor with one entry per
+    row: float selected where > 0 (kind '>0') or where != 0 (kind '!=0'), bool (kind 'bool'); scale None or a float tensor with
+    one entry per row (taken detached: nothing flows into it); drop None or a bool / uint8 tensor per row.
     -> (total 0-dim, rest (3 T,) detached = [weighted terms, denominators, unweighted means])."""
 
     @staticmethod
@@ -843,14 +768,17 @@ class LossAssemblyFn(Function):
                     if m.dtype != torch.bool:
                         raise TypeError("kind 'bool' needs a bool mask")
                     mk = 2
-                else:
+                elif kind in (">0", "!=0"):
                     m = _f32(mask).reshape(-1)
-                    mk = 1
-                n = m.numel()
+                    mk = 1 if kind == ">0" else 3
+                else:
+                    raise ValueError(f"term {t}: mask kind {kind!r} is none of '>0', '!=0', 'bool'")
+                if m.numel() != n:                         # (never regrouped into the mask's rows)
+                    raise ValueError(f"term {t}: values {tuple(x2.shape)} but a mask of {m.numel()} rows")
                 mp = L.ptr(m)
                 keep.append(m)
-            if x2.numel() == 0 or x2.numel() % n:
-                raise ValueError(f"term {t}: {x2.numel()} values do not make {n} rows")
+            if x2.numel() == 0:
+                raise ValueError(f"term {t}: no values")
             x2 = x2.reshape(n, -1)
             sp = dp = None
             if scale is not None:

@@ -501,31 +501,6 @@ __global__ __launch_bounds__(256) void ray_loss_bwd_kernel(const float* __restri
     for (int k = 0; k < 2; ++k) d_flo[i * 2 + k] = gf * 2.f * (flo[i * 2 + k] - flo_at[i * 2 + k]) * cn * s;
 }
 
-// x[m].mean() of a trainer's loss assembly (moda.py:540-640) without the boolean gather: out = sum(x * m) / (k * sum(m)), x (N, k),
-// m (N) any non-zero = selected; one workgroup.  Backward: dx = g * m / (k * sum(m)).
-__global__ __launch_bounds__(1024) void masked_mean_fwd_kernel(const float* __restrict__ x, const float* __restrict__ m, int N, int k,
-                                                               float* __restrict__ out) {
-    __shared__ float red[16];
-    float sx = 0.f, sm = 0.f;
-    for (int i = threadIdx.x; i < N; i += 1024) {
-        const float mk = m[i] != 0.f ? 1.f : 0.f;
-        sm += mk;
-        float r = 0.f;
-        for (int c = 0; c < k; ++c) r += x[(long long)i * k + c];
-        sx += r * mk;
-    }
-    const float tx = block_sum_1024(sx, red);
-    const float tm = block_sum_1024(sm, red);
-    if (threadIdx.x == 0) { out[0] = tx / (tm * (float)k); out[1] = tm * (float)k; }
-}
-
-__global__ __launch_bounds__(256) void masked_mean_bwd_kernel(const float* __restrict__ m, int N, int k, const float* __restrict__ cnt,
-                                                              const float* __restrict__ g, float* __restrict__ dx) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N * k) return;
-    dx[i] = m[i / k] != 0.f ? g[0] / cnt[1] : 0.f;
-}
-
 // Per-row distance of two (N, F) arrays, the small reductions of the loss heads (loss_utils.py:200 feat_err, :216-221 the
 // reprojection error: ||a - b||_2;  rendering.py:573-577 the rendered-feature error: mean_c (a - b)^2) -- one thread per row.
 // Backward: da = g (a - b) / ||a - b|| (0 where the norm is 0, torch's norm backward), or g 2 (a - b) / F;  db = -da when asked.
@@ -553,92 +528,6 @@ __global__ __launch_bounds__(256) void row_dist_kernel(const float* __restrict__
         if (db) db[i * F + c] = -d;
     }
 }
-
-// The weighted sum of a trainer's loss terms (moda.py:540-705) as ONE launch each way: term t = weight_t * mean over the selected
-// rows of x_t (n_t, k_t); rows are selected by a mask of one of three kinds (or all of them).  A single workgroup walks the terms
-// (a few thousand rays each): out[0] = the sum, out[1 + t] = term t, out[1 + T + t] = its denominator k_t * #selected.
-constexpr int kMaxLossTerms = 16;
-struct LossTerms { moda_loss_term t[kMaxLossTerms]; int n; };
-
-DEVINL bool loss_row_selected(const moda_loss_term& q, long long i) {
-    if (q.mask_kind == 1) return ((const float*)q.mask)[i] > 0.f;
-    if (q.mask_kind == 2) return ((const unsigned char*)q.mask)[i] != 0;
-    if (q.mask_kind == 3) return ((const float*)q.mask)[i] != 0.f;
-    return true;
-}
-
-// sums of one term over the rows lane, lane + 64, ...: eight rows per lane in flight
-template <int MK, bool K1>
-DEVINL void loss_term_sums(const moda_loss_term& q, int lane, float& sx, float& sm) {
-    for (long long base = 0; base < q.n; base += 64 * 8) {
-        float xs[8], ms[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const long long i = base + u * 64 + lane;
-            const bool ok = i < q.n;
-            const long long ii = ok ? i : 0;
-            bool sel = ok;                      // (the row index is clamped: every load is unconditional, nothing short-circuits)
-            if (MK == 1) { const float mv = ((const float*)q.mask)[ii]; sel = ok & (mv > 0.f); }
-            if (MK == 2) { const unsigned char mv = ((const unsigned char*)q.mask)[ii]; sel = ok & (mv != 0); }
-            if (MK == 3) { const float mv = ((const float*)q.mask)[ii]; sel = ok & (mv != 0.f); }
-            ms[u] = sel ? 1.f : 0.f;
-            if (K1) {
-                xs[u] = q.x[ii];
-            } else {
-                float r = 0.f;
-                for (int c = 0; c < q.k; ++c) r += q.x[ii * q.k + c];
-                xs[u] = r;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            sm += ms[u];
-            sx += ms[u] != 0.f ? xs[u] : 0.f;
-        }
-    }
-}
-
-__global__ __launch_bounds__(1024) void loss_terms_fwd_kernel(LossTerms a, float* __restrict__ out) {
-    __shared__ float term_s[kMaxLossTerms];
-    // (readfirstlane: the wave index is uniform, so the term is fetched with scalar loads from the kernel arguments; indexed by
-    //  a per-lane value the compiler would copy all sixteen terms to scratch first -- 20-30 us of dispatch + spill for this kernel)
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (wave < a.n) {                       // one wavefront per term (16 waves, <= 16 terms): the terms are summed concurrently
-        const moda_loss_term q = a.t[wave];
-        float sx = 0.f, sm = 0.f;
-        // the mask kind and k == 1 are chosen ONCE, outside the row loop: with the tests inside it every load sat behind a branch
-        // and the wave waited for each of them in turn (27 us for 8 x 2048 rows)
-        switch (q.mask_kind * 2 + (q.k == 1 ? 1 : 0)) {
-            case 0: loss_term_sums<0, false>(q, lane, sx, sm); break;
-            case 1: loss_term_sums<0, true>(q, lane, sx, sm); break;
-            case 2: loss_term_sums<1, false>(q, lane, sx, sm); break;
-            case 3: loss_term_sums<1, true>(q, lane, sx, sm); break;
-            case 4: loss_term_sums<2, false>(q, lane, sx, sm); break;
-            case 5: loss_term_sums<2, true>(q, lane, sx, sm); break;
-            case 6: loss_term_sums<3, false>(q, lane, sx, sm); break;
-            default: loss_term_sums<3, true>(q, lane, sx, sm); break;
-        }
-        const float tx = wave_sum(sx), tm = wave_sum(sm);
-        const float den = tm * (float)q.k;
-        const float term = q.weight * (tx / den);        // nothing selected: 0 / 0 = NaN, as the mean of an empty selection
-        if (lane == 0) { term_s[wave] = term; out[1 + wave] = term; out[1 + a.n + wave] = den; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float total = 0.f;
-        for (int t = 0; t < a.n; ++t) total += term_s[t];    // in term order, as the reference adds them
-        out[0] = total;
-    }
-}
-
-__global__ __launch_bounds__(256) void loss_terms_bwd_kernel(LossTerms a, const float* __restrict__ out, const float* __restrict__ g) {
-    const moda_loss_term q = a.t[blockIdx.y];
-    if (!q.dx) return;
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= q.n * q.k) return;
-    q.dx[e] = loss_row_selected(q, e / q.k) ? g[0] * q.weight / out[1 + a.n + blockIdx.y] : 0.f;
-}
-
 
 // ---- the Sinkhorn iterations as ONE persistent launch (round 5) ----------------------------------------------------------
 // feat_match's 20 iterations are 40 dependent matrix-vector sweeps forward (loss_utils.py:361-370) and 38 backward, each over the
@@ -994,38 +883,6 @@ extern "C" int moda_ray_loss(const float* rgb, const float* sil, const float* fl
         hipLaunchKernelGGL(ray_loss_fwd_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, rgb, sil, flo, valid, img_at, sil_at, vis_at,
                            flo_at, cfd_at, (int)N, (int)training, img_loss, sil_loss, flo_loss, sil_flo, stats);
     }
-    return (int)hipGetLastError();
-}
-
-extern "C" int moda_masked_mean(const float* x, const float* mask, int64_t N, int32_t k, float* out2, const float* g, float* dx,
-                                void* stream) {
-    if (N <= 0 || k < 1 || N > (1 << 24) || !mask || !out2) return MODA_EINVAL;
-    if (dx) {
-        if (!g) return MODA_EINVAL;
-        hipLaunchKernelGGL(masked_mean_bwd_kernel, dim3((unsigned)((N * k + 255) / 256)), dim3(256), 0, (hipStream_t)stream, mask, (int)N,
-                           (int)k, out2, g, dx);
-    } else {
-        if (!x) return MODA_EINVAL;
-        hipLaunchKernelGGL(masked_mean_fwd_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, mask, (int)N, (int)k, out2);
-    }
-    return (int)hipGetLastError();
-}
-
-extern "C" int moda_loss_terms(const moda_loss_term* terms, int32_t n_terms, float* out, const float* g, void* stream) {
-    if (n_terms <= 0) return 0;
-    if (!terms || n_terms > kMaxLossTerms || !out) return MODA_EINVAL;
-    LossTerms a;
-    a.n = n_terms;
-    long long most = 0;
-    for (int t = 0; t < n_terms; ++t) {
-        const moda_loss_term& q = terms[t];
-        if (!q.x && !g) return MODA_EINVAL;
-        if (q.n < 1 || q.k < 1 || q.n > (1 << 24) || q.mask_kind < 0 || q.mask_kind > 3 || (q.mask_kind && !q.mask)) return MODA_EINVAL;
-        a.t[t] = q;
-        if (q.n * q.k > most) most = q.n * q.k;
-    }
-    if (g) hipLaunchKernelGGL(loss_terms_bwd_kernel, dim3((unsigned)((most + 255) / 256), (unsigned)n_terms), dim3(256), 0, (hipStream_t)stream, a, out, g);
-    else hipLaunchKernelGGL(loss_terms_fwd_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a, out);
     return (int)hipGetLastError();
 }
 

@@ -14,8 +14,8 @@
 //   root smoothness          (:486-517 compute_root_sm_2nd_loss, geom_utils.py:1196-1205 rot_angle)  one workgroup forward; the
 //               backward is a gather: one thread per frame sums the up to three triples the frame belongs to, in a fixed order.
 //   loss assembly            (moda.py:517-768)  total <- carry_t * total + weight_t * mean_t over the terms in order, times total_wt:
-//               one wavefront per term forward (the row-to-lane map and the order of every sum are those of moda_loss_terms, so a
-//               call without scale / drop / carry gives that kernel's bits), one launch backward.
+//               one wavefront per term forward, one launch backward.  loss_utils.total_loss (no scale / drop / carry) and
+//               masked_mean (one term of weight 1) are calls of the same entry.
 // No float atomics anywhere: for given inputs every sum has one fixed tree.  Device memory is written by plain vector stores.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -327,7 +327,8 @@ DEVINL bool asm_row_selected(const moda_asm_term& q, long long i) {
     return true;
 }
 
-// sums of one term over the rows lane, lane + 64, ...: eight rows per lane in flight (moda_loss_terms' map and order)
+// sums of one term over the rows lane, lane + 64, ...: eight rows per lane in flight.  The map and the order of every sum are
+// pinned bit for bit by tests/golden/g31_total_loss_bits.npz (recorded from the kernel this one replaced): keep both.
 template <int MK, bool K1, bool SD>
 DEVINL void asm_term_sums(const moda_asm_term& q, int lane, float& sx, float& sm) {
     for (long long base = 0; base < q.n; base += 64 * 8) {
@@ -365,7 +366,9 @@ DEVINL void asm_term_sums(const moda_asm_term& q, int lane, float& sx, float& sm
 
 template <bool SD>
 DEVINL void asm_term_dispatch(const moda_asm_term& q, int lane, float& sx, float& sm) {
-    switch (q.mask_kind * 2 + (q.k == 1 ? 1 : 0)) {               // chosen once, outside the row loop
+    // the mask kind and k == 1 are chosen ONCE, outside the row loop: with the tests inside it every load sat behind a branch
+    // and the wave waited for each of them in turn (27 us for 8 x 2048 rows)
+    switch (q.mask_kind * 2 + (q.k == 1 ? 1 : 0)) {
         case 0: asm_term_sums<0, false, SD>(q, lane, sx, sm); break;
         case 1: asm_term_sums<0, true, SD>(q, lane, sx, sm); break;
         case 2: asm_term_sums<1, false, SD>(q, lane, sx, sm); break;
@@ -380,8 +383,10 @@ DEVINL void asm_term_dispatch(const moda_asm_term& q, int lane, float& sx, float
 // out[0] = total, out[1 + t] = weight_t * mean_t, out[1 + T + t] = den_t = k_t * #selected, out[1 + 2 T + t] = mean_t
 __global__ __launch_bounds__(1024) void loss_asm_fwd_kernel(AsmTerms a, float* __restrict__ out) {
     __shared__ float term_s[kMaxTerms];
+    // (readfirstlane: the wave index is uniform, so the term is fetched with scalar loads from the kernel arguments; indexed by
+    //  a per-lane value the compiler would copy all sixteen terms to scratch first -- 20-30 us of dispatch + spill for this kernel)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (wave < a.n) {                                              // one wavefront per term
+    if (wave < a.n) {                       // one wavefront per term (16 waves, <= 16 terms): the terms are summed concurrently
         const moda_asm_term q = a.t[wave];
         float sx = 0.f, sm = 0.f;
         if (q.scale || q.drop) asm_term_dispatch<true>(q, lane, sx, sm);

@@ -248,10 +248,13 @@ def visibility_loss(mlp, embed, xyz_pos, w_pos, bound, chunk, rng=None):
 
 
 def masked_mean(x, mask):
-    """`x[mask].mean()` as the reference's loss assembly writes it (moda.py:540-640), as one kernel each way and without the
-    boolean gather's host sync: x (N, k) | (N,), mask (N, 1) | (N,) bool or float (non-zero = selected).  NaN when nothing is
-    selected, as the reference's mean of an empty selection."""
-    return A.MaskedMeanFn.apply(x, mask)
+    """`x[mask].mean()` as the reference's loss assembly writes it (moda.py:540-640), without the boolean gather's host sync:
+    x (N, k) | (N,), mask (N, 1) | (N,) bool or float (non-zero = selected).  NaN when nothing is selected, as the reference's
+    mean of an empty selection.  One term of weight 1 of the loss assembly (moda_loss_assembly), one launch each way: the sum is
+    formed in the assembly's order (per lane over the rows lane, lane + 64, ..., then one wave butterfly), and the rows are
+    SELECTED, not multiplied by the mask -- a NaN or inf in an unselected row does not reach the mean, as in `x[mask]`."""
+    kind = "bool" if mask.dtype == torch.bool else "!=0"
+    return A.LossAssemblyFn.apply([(1.0, mask, kind, None, None, 1.0)], 1.0, x)[0]
 
 
 # the weights of moda.py's loss assembly (flags moda.py:153-162; the visibility term's 0.01 is written out at :702)
@@ -265,8 +268,9 @@ def total_loss(rendered, weights=None):
     `forward_loss` below is that assembly).  img_wt * img_loss_samp[sil > 0].mean() + sil_wt * sil_loss_samp[vis > 0].mean() +
     frnd_wt * frnd_loss_samp[sil > 0].mean() + 2 flow_wt * flo_loss_samp[sil_at_samp_flo].mean() + feat_wt * feat_err[sil > 0]
     .mean() + proj_wt * proj_err[sil > 0].mean() + vis_wt * vis_loss + cyc_wt * frame_cyc_dis.mean() -- the terms whose keys
-    the dict holds, as ONE launch forward and one backward (moda_loss_terms) instead of ~55 eager ops with a boolean gather
-    (and its host sync) per term.  -> (total, {term name: weighted term, detached}).  moda.py itself cannot be imported here
+    the dict holds, as ONE launch forward and one backward instead of ~55 eager ops with a boolean gather (and its host sync)
+    per term: the assembly `forward_loss` runs (moda_loss_assembly) without scale, drop, carry and total_wt, in this function's
+    own term order (vis before cyc).  -> (total, {term name: weighted term, detached}).  moda.py itself cannot be imported here
     (absl, mcubes ...): restated from the cited lines, checked against the plain-torch restatement (oracle/torch_ref.py)."""
     w = dict(LOSS_WEIGHTS)
     w.update(weights or {})
@@ -280,10 +284,10 @@ def total_loss(rendered, weights=None):
     for name, key, wt, mask, kind in plan:
         if key in rendered:
             names.append(name)
-            spec.append((wt, mask, kind))
+            spec.append((wt, mask, kind, None, None, 1.0))
             xs.append(rendered[key])
-    total, terms = A.LossTermsFn.apply(spec, *xs)
-    return total, {n: terms[i] for i, n in enumerate(names)}
+    total, rest = A.LossAssemblyFn.apply(spec, 1.0, *xs)
+    return total, {n: rest[i] for i, n in enumerate(names)}
 
 
 # ---- the stage between render_rays and backward() with the reference's own flags (loss_flt, rm_novp, root_sm) ------------------

@@ -197,3 +197,22 @@ def assembly_case(N=37, seed=29):
     return rendered, opts
 
 
+# (N, wide, empty): N = 37 lies under one wave, 64 fills one, 577 = 512 + 64 + 1 is one full eight-row block of the lane loop, one
+# more wave row and a tail of one; `wide` gives the bool-masked and the unmasked term three columns beside img's; `empty` leaves
+# the bool mask without a selected row (a NaN term and a NaN total)
+TOTAL_LOSS_BITS_CASES = ((37, False, False), (64, True, False), (577, False, False), (577, True, False), (37, True, True),
+                         (577, False, True))
+TOTAL_LOSS_BITS_INPUTS = ("img_loss_samp", "sil_loss_samp", "frnd_loss_samp", "flo_loss_samp", "feat_err", "proj_err", "vis_loss",
+                          "frame_cyc_dis")
+
+
+def total_loss_bits_case(N, wide, empty):
+    """`rendered` for total_loss with all eight terms: k = 1 and 3, no mask / float `> 0` / bool masks, the 0-dim vis_loss and the
+    zero-weight feat term (feat_wt's default).  Plain normals, so every sum depends on the order it is formed in."""
+    rng = np.random.default_rng(3100 + 7 * N + 2 * wide + empty)
+    f = lambda *sh: np.abs(rng.normal(size=sh)).astype(np.float32)
+    k = 3 if wide else 1
+    return dict(img_loss_samp=f(N, 3), sil_loss_samp=f(N, 1), frnd_loss_samp=f(N, 1), flo_loss_samp=f(N, k), feat_err=f(N, 1),
+                proj_err=f(N, 1), vis_loss=f(), frame_cyc_dis=f(N, k) if wide else f(N),
+                sil_at_samp=(rng.random((N, 1)) > 0.3).astype(np.float32), vis_at_samp=(rng.random((N, 1)) > 0.1).astype(np.float32),
+                sil_at_samp_flo=np.zeros((N, 1), bool) if empty else rng.random((N, 1)) > 0.5)

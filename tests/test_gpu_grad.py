@@ -1213,7 +1213,7 @@ def test_s3im_kernel_against_the_torch_restatement():
 
 def test_ray_loss_and_masked_mean_kernels_against_torch():
     """moda_ray_loss (the img / sil / flo terms of rendering.py:518-571 with the silhouette class balance :535-539 and the
-    confidence normalisation :549-556, one kernel each way) and moda_masked_mean (x[m].mean() of moda.py:540-640) against the
+    confidence normalisation :549-556, one kernel each way) and loss_utils.masked_mean (x[m].mean() of moda.py:540-640) against the
     same arithmetic written with torch ops as the reference writes it (boolean gathers and `if ... .sum() > 0`), values and
     gradients, training and eval, including the degenerate batches (no silhouette pixel; no valid flow pixel)."""
     from moda_amd import autograd as A, loss_utils as LU
@@ -1279,10 +1279,33 @@ def test_ray_loss_and_masked_mean_kernels_against_torch():
     assert abs(float(got) - float((x1 * m1).sum() / m1.sum())) < 1e-6
 
 
+@pytest.mark.parametrize("bool_mask", [True, False])
+def test_masked_mean_selects_rows_a_nan_in_an_unselected_row_stays_out(bool_mask):
+    """masked_mean is `x[mask].mean()`: the rows are selected, not multiplied by the mask, so a NaN and an inf in unselected rows
+    reach neither the value (the float64 gather within 2e-6) nor the gradient (exactly 0 at those rows).  N = 577 = 512 + 64 + 1:
+    a full eight-row block of the lane loop, one more wave row and a tail; a bool mask and a float one (selected where != 0)."""
+    from moda_amd import loss_utils as LU
+    N = 577
+    x = synth.normal(43, "mm/nan/x", (N, 3))
+    m = synth.uniform(43, "mm/nan/m", (N, 1)) < 0.4
+    off = np.flatnonzero(~m[:, 0])
+    x[off[0], 1], x[off[-1], 0] = np.nan, np.inf
+    xg, xc = T(x).requires_grad_(True), TC(x).double().requires_grad_(True)
+    mf = np.where(m, -0.5, 0.0).astype(np.float32)                    # float form: any non-zero value selects, a negative one too
+    got = LU.masked_mean(xg, T(m) if bool_mask else T(mf))
+    want = xc[TC(m)[:, 0]].mean()
+    got.backward(); want.backward()
+    assert np.isfinite(float(want)) and abs(float(got) - float(want)) < 2e-6 * abs(float(want))
+    assert rel_err(np_(xg.grad)[m[:, 0]], xc.grad.numpy()[m[:, 0]]) < 2e-6
+    assert float(xg.grad[T(~m[:, 0])].abs().max()) == 0
+    with pytest.raises(ValueError):
+        LU.masked_mean(xg, T(m[:-1]))
+
+
 @pytest.mark.parametrize("N", [2048, 37, 70001])
 @pytest.mark.parametrize("keys", ["all", "render_only"])
 def test_total_loss_matches_the_boolean_gather_form(N, keys):
-    """moda_amd.loss_utils.total_loss (moda_loss_terms: one launch each way) against the reference's assembly as written
+    """moda_amd.loss_utils.total_loss (moda_loss_assembly: one launch each way) against the reference's assembly as written
     (moda.py:540-705: weight * x[mask].mean() per term, boolean gathers; oracle/torch_ref.py total_loss), value, every term and
     the gradient at every input; with the flags' default weights (feat_wt = 0: a zero-weight term still counts) and others."""
     from moda_amd import loss_utils as LU

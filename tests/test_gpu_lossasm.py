@@ -432,6 +432,45 @@ def test_total_loss_is_forward_loss_with_the_three_flags_off(without):
         assert float(ta) == float(tb)
 
 
+def _total_loss_bits():
+    import importlib.util
+    import os
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("gen_golden_total_loss_bits", os.path.join(here, "gen_golden_total_loss_bits.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen, np.load(os.path.join(here, "g31_total_loss_bits.npz"))
+
+
+@pytest.mark.parametrize("case", cases.TOTAL_LOSS_BITS_CASES, ids=lambda c: f"n{c[0]}-wide{int(c[1])}-empty{int(c[2])}")
+def test_total_loss_reproduces_the_recorded_bits(case):
+    """total_loss through the one assembly against tests/golden/g31_total_loss_bits.npz, which the generator beside it recorded on
+    an MI355X at the last commit where total_loss had a kernel pair of its own: the total, every weighted term and every input
+    gradient, BIT FOR BIT (compared as uint32, so that the NaN term and total of the `empty` cases count too).  N = 37 / 64 / 577
+    (under one wave; one wave; an eight-row block + one wave row + a tail of one), k = 1 and 3, masks none / float > 0 / bool, the
+    0-dim vis_loss, the zero-weight feat term, and a term with nothing selected beside terms whose gradients must not move."""
+    gen, want = _total_loss_bits()
+    got = gen.run_case(*case)
+    name = gen.case_name(*case)
+    keys = [k.split("/", 1)[1] for k in want.files if k.startswith(name + "/")]
+    assert sorted(keys) == sorted(got) and len(keys) == 1 + 8 + 8
+    for k in keys:
+        assert got[k].dtype == np.uint32 and np.array_equal(got[k], want[f"{name}/{k}"]), k
+    if case[2]:
+        total, flo = got["total"].view(np.float32), got["term_flo"].view(np.float32)
+        assert np.isnan(total) and np.isnan(flo) and not got["grad_flo_loss_samp"].any()
+        assert np.isfinite(got["term_img"].view(np.float32)) and got["grad_img_loss_samp"].any()
+
+
+def test_total_loss_refuses_values_that_do_not_match_the_mask_rows():
+    """A value tensor whose leading dimension is not the mask's row count is refused, not regrouped into mask rows."""
+    from moda_amd import loss_utils as LU
+    rd = {k: T(v) for k, v in cases.total_loss_bits_case(37, False, False).items()}
+    rd["img_loss_samp"] = rd["img_loss_samp"].reshape(3, 37)
+    with pytest.raises(ValueError):
+        LU.total_loss(rd)
+
+
 def test_filter_assembly_backward_captured_and_replayed():
     """Filter + root term + assembly + backward captured once into a graph and replayed three times with new inputs copied into
     the static buffers: every replay equals the eager result on a second filter fed the same sequence -- total, gradients, flags
