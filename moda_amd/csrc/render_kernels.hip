@@ -1340,7 +1340,7 @@ __global__ __launch_bounds__(1024) void dbg_poison_lds_kernel(unsigned pattern, 
 #define ST(s) ((hipStream_t)(s))
 #define LAUNCH_RC() ((int)hipGetLastError())
 
-extern "C" int moda_abi_version(void) { return 10; }
+extern "C" int moda_abi_version(void) { return 11; }
 
 extern "C" uint64_t moda_stream_capture_id(void* stream) {
     hipStreamCaptureStatus status = hipStreamCaptureStatusNone;

@@ -94,7 +94,7 @@ def test_new_entries_are_bound_and_declared():
     declared = set(re.findall(r"\b(moda_[a-z0-9_]+)\s*\(", hdr))
     for name in NEW_ENTRIES:
         assert name in _lib.EXPORTS and name in declared, name
-    assert _lib.ABI_VERSION == 10 and _lib.load().moda_abi_version() == 10
+    assert _lib.ABI_VERSION == 11 and _lib.load().moda_abi_version() == 11
     assert int(re.search(r"#define MODA_KMEANS_MAX_K (\d+)", hdr).group(1)) == B.MAX_K == 64
     assert int(re.search(r"#define MODA_MC_SCAN_TILE (\d+)", hdr).group(1)) == B._SCAN_TILE
 

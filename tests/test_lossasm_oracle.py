@@ -160,7 +160,7 @@ def test_new_entries_are_bound_and_declared():
     declared = set(re.findall(r"\b(moda_[a-z0-9_]+)\s*\(", hdr))
     for name in NEW_ENTRIES:
         assert name in _lib.EXPORTS and name in declared, name
-    assert _lib.ABI_VERSION == 10 and _lib.load().moda_abi_version() == 10
+    assert _lib.ABI_VERSION == 11 and _lib.load().moda_abi_version() == 11
     assert ctypes.sizeof(_lib.AsmTerm) == 64
     from moda_amd import build
     assert "lossasm_kernels.hip" in build.SOURCES

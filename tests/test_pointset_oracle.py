@@ -93,7 +93,7 @@ def test_point_set_entries_declared_bound_and_exported():
         assert name in declared, f"{name} is not declared in include/moda_hip.h"
         assert name in _lib.EXPORTS, f"{name} is not bound in moda_amd/_lib.py"
         assert hasattr(lib, name), f"{name} is not exported by the built library"
-    assert lib.moda_abi_version() == _lib.ABI_VERSION == 10
+    assert lib.moda_abi_version() == _lib.ABI_VERSION == 11
     # shape refusals need no device: they come before any pointer is looked at
     assert lib.moda_nn_fwd(None, None, 1, 4, 0, None, None, None, None) == -2
     assert lib.moda_nn_fwd(None, None, 0, 4, 4, None, None, None, None) == -2

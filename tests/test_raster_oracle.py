@@ -293,7 +293,7 @@ def test_raster_entries_declared_bound_and_exported():
         assert name in declared, f"{name} is not declared in include/moda_hip.h"
         assert name in _lib.EXPORTS, f"{name} is not bound in moda_amd/_lib.py"
         assert hasattr(lib, name), f"{name} is not exported by the built library"
-    assert lib.moda_abi_version() == _lib.ABI_VERSION == 10
+    assert lib.moda_abi_version() == _lib.ABI_VERSION == 11
 
     # shape refusals need no device: they come before any pointer is looked at
     def fwd(B, V, F, S):

@@ -71,7 +71,7 @@ def test_entries_are_bound_and_declared():
     declared = set(re.findall(r"\b(moda_[a-z0-9_]+)\s*\(", hdr))
     for name in ("moda_sinkdiv_ws_bytes", "moda_sinkdiv"):
         assert name in _lib.EXPORTS and name in declared, name
-    assert _lib.ABI_VERSION == 10 and _lib.load().moda_abi_version() == 10
+    assert _lib.ABI_VERSION == 11 and _lib.load().moda_abi_version() == 11
     from moda_amd import build
     assert "sinkdiv_kernels.hip" in build.SOURCES
     assert "MODA_SINKDIV_MAX_STEPS 24" in hdr and "MODA_SINKDIV_MAX_POINTS 4096" in hdr
