@@ -918,6 +918,50 @@ int moda_s3im(const float* rgb, const float* tar, const float* mask, int64_t N, 
  * result depends on LDS it has not written shows up as a difference between two patterns). */
 int moda_dbg_poison_lds(uint32_t pattern, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Root (camera) poses (moda_amd/csrc/rootpose_kernels.hip; additive entries of ABI 11: no existing signature changed).  One
+ * thread per row, fp32; nothing allocates, synchronises or reads back, every launch goes to `stream`, so the chain can be
+ * captured into a graph.  No float atomics and no contraction: the same bits on every run.
+ * ------------------------------------------------------------------------ */
+#define MODA_ROOT_RAW_NONE   0   /* no refine_rt: rtk[:, :3] is the root transform itself (the modules' own (bs, 1, 12) output) */
+#define MODA_ROOT_RAW_BASE   1   /* create_base_se3 (moda.py:1025-1033): identity rotation, t = (0, 0, 0.3); rt_raw unused */
+#define MODA_ROOT_RAW_ROWS   2   /* rt_raw (n, raw_rows, 4), row-aligned */
+#define MODA_ROOT_RAW_BY_ID  3   /* rt_raw (T, raw_rows, 4), gathered by ids[i] */
+
+/* The tail of RTExplicit / RTHead / RTExpMLP (nerf.py:307-344, 382-470) composed with refine_rt (moda.py:1450-1466) and the
+ * intrinsics row of convert_root_pose (moda.py:1447), per row i:
+ *   base   se3 (T, cols)|NULL gathered by ids[i] (int32, or int64 where ids64): t_b = 0.1 se3[0:3]; cols 7: R_b =
+ *          quaternion_to_matrix(q / max(|q|, 1e-12)) in its 2 / |q|^2 form; cols 6: R_b = so3_exp(se3[3:6]).  NULL: identity.
+ *   delta  delta (n, delta_cols)|NULL, the MLP's output row, the same two forms (6: so3_exp, 7: quaternion).
+ *          With BOTH given (RTExpMLP): every base value x becomes x * 10 - x * 9 (two roundings and a difference, nerf.py:456)
+ *          and its gradient is 10x; t = t_b + R_b t_d, R = R_b R_d (nerf.py:464-465).
+ *   so3_exp(w) = f1 hat(w) + f2 hat(w)^2 + I, theta = sqrt(max(sum(w * w), 1e-4)), f1 = sin(theta) / theta, f2 = (1 - cos(theta)) /
+ *          theta^2 (pytorch3d's so3_exponential_map restated; below the clamp theta = 0.01 carries no gradient).
+ *   refine raw_mode (MODA_ROOT_RAW_*): t = t_raw / obj_scale + R_raw t, R = R_raw R; raw_rows 3 or 4; rt_raw gets no gradient.
+ *   rtk    (n, out_rows, 4), out_rows 3 or 4; row 3 = ks[dataid[i]] (ks (n_ks, 4), dataid as ids) or (0, 0, 0, 1) when ks NULL.
+ * An id outside [0, T) (a dataid outside [0, n_ks)) is counted in status[0] (status[1]) by the FORWARD call, which ADDS to the
+ * 4 int32 the caller zeroed, and nothing is read through it: its rtk row (its K row) is NaN, its gradient rows are 0.
+ * g_rtk == NULL: forward.  g_rtk (n, out_rows, 4) != NULL: backward -- d_rows (n, cols) for the gathered base rows (sum them
+ * into the table with moda_id_rows_sum), d_delta (n, delta_cols), and d_ks_rows (n, 4)|NULL; every element written. */
+int moda_root_pose(const float* se3, int64_t T, int32_t cols, const void* ids, int32_t ids64, int64_t n, const float* delta,
+                   int32_t delta_cols, const float* rt_raw, int32_t raw_mode, int32_t raw_rows, float obj_scale, const float* ks,
+                   const void* dataid, int32_t dataid64, int64_t n_ks, int32_t out_rows, float* rtk, const float* g_rtk,
+                   float* d_rows, float* d_delta, float* d_ks_rows, int32_t* status, void* stream);
+
+/* The backward of a gather: d_table (T, C) = sum of rows[i] (n, C) over ids[i] == t, C <= 8, added in increasing i -- one lane
+ * per table row, the ids staged through LDS in tiles of 1024 and read as a broadcast.  The order is fixed, so the bits do not
+ * depend on the run or on `lanes` (lanes per workgroup: 0 = 256, else a multiple of 64 up to 1024).  Every element of d_table
+ * is written (no memset needed); an id outside [0, T) adds nowhere.  T <= 2^31 - 1. */
+int moda_id_rows_sum(const float* rows, const void* ids, int32_t ids64, int64_t n, int64_t T, int32_t C, float* d_table,
+                     int32_t lanes, void* stream);
+
+/* prepare_ray_cams (moda.py:1036-1046): rtk (n, 4, 4), kaug (n, 4) -> Rmat (n, 3, 3) = rtk[:, :3, :3], Tmat (n, 3) = rtk[:, :3, 3],
+ * Kinv (n, 3, 3) = Kmatinv(K2inv(kaug) @ K2mat(rtk[:, 3])) in the quotient forms of geom_utils.py:629-652 (1 / fx, -px / fx).
+ * d_rtk == NULL: forward.  d_rtk (n, 4, 4) != NULL: backward from g_Rmat, g_Tmat, g_Kinv (each may be NULL = zero), the K row
+ * included; kaug gets no gradient. */
+int moda_ray_cams(const float* rtk, const float* kaug, int64_t n, float* Rmat, float* Tmat, float* Kinv, const float* g_Rmat,
+                  const float* g_Tmat, const float* g_Kinv, float* d_rtk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,3 +33,7 @@ from .train_utils import GradClipper, clip_grad, grad_group, GRAD_GROUPS  # noqa
 from . import samples_loss  # noqa: F401
 from .samples_loss import SamplesLoss  # noqa: F401
 from .loss_utils import bone_loc_loss  # noqa: F401
+from .feeders import RTHead, RTExplicit, RTExpMLP, id_rows_sum  # noqa: F401
+from .geom_utils import K2mat, K2inv, Kmatinv, mat2K, refine_rt, create_base_se3, prepare_ray_cams  # noqa: F401
+from . import root_pose  # noqa: F401
+from .root_pose import compute_rts, convert_root_pose  # noqa: F401

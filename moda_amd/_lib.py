@@ -148,6 +148,10 @@ _SIGNATURES = {
     # debiased Sinkhorn divergence of two point clouds (sinkdiv_kernels.hip): additive entries of ABI 9
     "moda_sinkdiv_ws_bytes": (_I64, [_I64, _I64]),
     "moda_sinkdiv": (_c.c_int, [_P, _P, _I64, _I64, _c.c_double, _c.c_double, _c.c_double, _P, _P, _P, _P, _P, _P]),
+    # root poses: module tails + refine_rt, gather backward, prepare_ray_cams (rootpose_kernels.hip): additive entries of ABI 11
+    "moda_root_pose": (_c.c_int, [_P, _I64, _I32, _P, _I32, _I64, _P, _I32, _P, _I32, _I32, _F32, _P, _P, _I32, _I64, _I32] + [_P] * 7),
+    "moda_id_rows_sum": (_c.c_int, [_P, _P, _I32, _I64, _I64, _I32, _P, _I32, _P]),
+    "moda_ray_cams": (_c.c_int, [_P, _P, _I64] + [_P] * 8),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -71,6 +71,18 @@ TRAIN_WEIGHTS = dict(img_wt=1.0, sil_wt=0.1, frnd_wt=0.01, flow_wt=1.0, feat_wt=
 PREPASS_PRECISION = {"bf16": "bf16", "bf16x3": "bf16x3", "bf16x6": "bf16x3", "fp32": "fp32"}
 
 
+def make_root_rts(n_frames, data_offset, num_freqs=6, t_embed_dim=128):
+    """The reference's default root-pose module (moda.py:376-379) over `n_frames` frames with weights from synth; the head's biases
+    are zero, as RTHead's constructor leaves them (nerf.py:319-322)."""
+    from moda_amd.feeders import RTExpMLP
+    m = RTExpMLP(n_frames, num_freqs, t_embed_dim, np.asarray(data_offset))
+    w, b = synth.linear_init(0, "nerf_root_rts.root_code", t_embed_dim, m.root_code.basis_mlp.in_features)
+    m.root_code.basis_mlp.load_state_dict({"weight": torch.from_numpy(w), "bias": torch.from_numpy(b)})
+    p = synth.nerf_params(0, "nerf_root_rts.mlp_rt", D=8, W=256, in_channels_xyz=t_embed_dim, in_channels_dir=0, out_channels=6)
+    m.mlp_rt.load_state_dict({k: torch.from_numpy(v if not k.endswith(".bias") else np.zeros_like(v)) for k, v in p.items()})
+    return m
+
+
 class TrainHarness:
     """One rank's training step as the reference's trainer runs it (nnutils/train_utils.py:950-969): forward + backward of
     the total loss assembled as nnutils/moda.py:540-640 does (default weights), DDP-style gradient all-reduce for world > 1,
@@ -83,7 +95,7 @@ class TrainHarness:
 
     def __init__(self, N=2048, S=128, B=25, precision="bf16", rank=0, world=1, dist=None, lr=2e-5, device=None, seed=1000,
                  rays_per_frame=4, fused_adamw=True, bucket=True, use_fine=False, with_unc=False, strong=False, clip_grad=False,
-                 clip_scale=10.0, default_losses=False, bone_loc=False):
+                 clip_scale=10.0, default_losses=False, bone_loc=False, root_pose=False):
         """use_fine / with_unc: the reference's LAST training stage (scripts/template.sh:59: --fine_steps 0 --use_unc): S/2 coarse
         depths rendered without gradients (rendering.py:91-107, here on the fused inference kernels in `PREPASS_PRECISION[precision]`),
         S/2 importance samples merged in, and the uncertainty network nerf_unc (8x256, moda.py:457-464) trained on
@@ -93,13 +105,17 @@ class TrainHarness:
         exchange and mean and before `opt.step()`.  Off by default: the benchmarked step is forward + backward + AdamW.
         default_losses: assemble the loss as the reference's default flags do (moda.py:167-168 loss_flt, rm_novp) through
         moda_amd.loss_utils.forward_loss with a device-resident LossFilter in line mode: ray i belongs to frame
-        i // rays_per_frame and to line i % rays_per_frame of it.  root_sm stays off (the synthetic scene has no camera table).
+        i // rays_per_frame and to line i % rays_per_frame of it.  root_sm stays off unless root_pose is set (the synthetic scene has no camera table).
         Off by default: the default path and the benchmarked step are unchanged.
         bone_loc (with default_losses): the bone-location term of moda.py:681-698 at the reference's bone_loc_reg = 0.1 inside the
         step -- the Sinkhorn divergence (moda_amd.samples_loss) between this harness's bone centres `bones_rst[:, :3] * 10` and
         1000 points drawn on a fixed synthetic rest mesh (synth.make_rest_mesh) from the preallocated uniforms `bone_u`, which
         draw() refills: replay and eager see the same samples.  The synthetic scene has no rest-pose head, so correct_bones is
-        not part of it.  Off by default."""
+        not part of it.  Off by default.
+        root_pose (with default_losses): the reference's default root poses (moda.py:83-85: root_opt, root_basis 'expmlp', no
+        cameras) inside the step -- an RTExpMLP over this harness's frames, one video [0, n_frames), weights from synth; every step
+        calls root_pose.compute_rts and the loss runs with root_sm=True on that table; the module's parameters join the optimiser,
+        the gradient bucket and the clipper's names (`nerf_root_rts.*`).  The rays stay the synthetic ones.  Off by default."""
         from moda_amd import sharding
         global DEV
         # strong=True: ONE batch of N rays (the one-rank run's rays) cut into contiguous per-rank ranges (sharding.shard_rays), so
@@ -148,6 +164,14 @@ class TrainHarness:
         self.rays = rays
         self.params = [p for m in self.models.values() if isinstance(m, torch.nn.Module) for p in m.parameters()]
         self.params += [self.models["bones_rst"], self.models["skin_aux"]]
+        self.root_pose, self.root_rts, self.aux_out = bool(root_pose), None, {}
+        if self.root_pose:
+            if not default_losses:
+                raise ValueError("TrainHarness: root_pose=True feeds the root-smoothness term of the default loss assembly (default_losses=True)")
+            self.n_frames = (N + rays_per_frame - 1) // rays_per_frame
+            self.data_offset = (0, self.n_frames)
+            self.root_rts = make_root_rts(self.n_frames, self.data_offset).to(self.dev).train()
+            self.params += list(self.root_rts.parameters())
         self.opts = make_opts(dist_corresp=True, use_corresp=True, use_ot=True)
         self.bound = np.asarray([0.2, 0.2, 0.2], np.float32)
         self.loss_buf = torch.zeros(2, device=self.dev)
@@ -190,7 +214,7 @@ class TrainHarness:
             self.frameid = (idx // rays_per_frame).to(torch.int32)
             self.errid = self.frameid * 512 + (idx % rays_per_frame).to(torch.int32)
             w = TRAIN_WEIGHTS
-            self.loss_opts = dict(loss_flt=True, rm_novp=True, root_sm=False, bone_loc_reg=0.1 if bone_loc else 0.0, lineload=True,
+            self.loss_opts = dict(loss_flt=True, rm_novp=True, root_sm=self.root_pose, bone_loc_reg=0.1 if bone_loc else 0.0, lineload=True,
                                   use_unc=self.with_unc,
                                   img_wt=w["img_wt"], sil_wt=w["sil_wt"], frnd_wt=w["frnd_wt"], flow_wt=w["flow_wt"],
                                   feat_wt=w["feat_wt"], proj_wt=w["proj_wt"], cyc_wt=w["cyc_wt"])
@@ -213,7 +237,10 @@ class TrainHarness:
         ref = {"coarse": "nerf_coarse"}
         out = [(f"{ref.get(k, k)}.{n}", p) for k, m in self.models.items() if isinstance(m, torch.nn.Module)
                for n, p in m.named_parameters()]
-        return out + [("bones", self.models["bones_rst"]), ("skin_aux", self.models["skin_aux"])]
+        out = out + [("bones", self.models["bones_rst"]), ("skin_aux", self.models["skin_aux"])]
+        if self.root_rts is not None:
+            out += [("nerf_root_rts." + n, p) for n, p in self.root_rts.named_parameters()]
+        return out
 
     def _clip(self):
         """The clipping stage, if enabled: three launches, nothing read back (eager and captured alike)."""
@@ -270,9 +297,15 @@ class TrainHarness:
             # detached: a tensor kept WITH its graph would keep the bones' gradient-accumulation node of this call alive, and that
             # node runs on the stream of the call that created it -- inside a later capture, on a stream that is not capturing
             self.bone_loc_value = bone_loc.detach()
+        rtk_all = None
+        if self.root_pose:                                             # moda.py:667-670 over compute_rts (moda.py:1468-1495)
+            from moda_amd.root_pose import compute_rts
+            rtk_all = compute_rts(self.root_rts, self.n_frames)
         loss, aux = forward_loss(r, self.loss_opts, loss_filter=self.loss_filter, errid=self.errid, frameid=self.frameid, progress=1.0,
-                                 bone_loc=bone_loc)
+                                 bone_loc=bone_loc, rtk_all=rtk_all, data_offset=self.data_offset if self.root_pose else None)
         loss.backward()
+        if self.root_pose:
+            self.aux_out = {k: aux[k].detach() for k in ("root_sm_loss", "root_rot_sm", "root_trn_sm")}
         keys = ("img_loss", "sil_loss", "feat_rnd_loss", "flo_loss", "feat_loss", "proj_loss", "visibility_loss", "cyc_loss")
         self.terms.copy_(torch.stack([aux[k] for k in keys]))
         self.terms[7].mul_(TRAIN_WEIGHTS["cyc_wt"])

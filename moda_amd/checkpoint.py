@@ -50,6 +50,33 @@ def _nerf_from_states(sd, cls=NeRF, **extra):
     return m
 
 
+def build_root_pose(states, data_offset, device='cuda'):
+    """states (a MoDA state dict) -> {'nerf_root_rts': module, 'ks_param': tensor | None}: the root-pose module of
+    moda.py:374-379 rebuilt from the `nerf_root_rts.*` keys -- RTExpMLP (`expmlp`) when the keys of its code and MLP are present,
+    RTExplicit (`exp`) when `nerf_root_rts.se3` is all there is; `delta` (a dataset with cameras) is read off the table's
+    width (6 columns: rotation vectors, 7: quaternions) -- and the intrinsics `ks_param` (moda.py:388-400)."""
+    from .feeders import RTExplicit, RTExpMLP
+    s = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in states.items()}
+    sd = _sub(s, 'nerf_root_rts')
+    if 'base_rt.se3' in sd and 'root_code.basis_mlp.weight' in sd and 'mlp_rt.rgb.0.weight' in sd:
+        se3, w = sd['base_rt.se3'], sd['root_code.basis_mlp.weight']
+        n_vids = len(data_offset) - 1
+        if n_vids < 1 or w.shape[1] % n_vids or (w.shape[1] // n_vids) % 2 != 1:               # in = n_vids (1 + 2F), nerf.py:359-361
+            raise ValueError(f"nerf_root_rts.root_code.basis_mlp.weight has {w.shape[1]} input columns, which is not n_vids * "
+                             f"(1 + 2F) for the {n_vids} videos of data_offset={list(data_offset)}")
+        m = RTExpMLP(se3.shape[0], (w.shape[1] // n_vids - 1) // 2, w.shape[0], np.asarray(data_offset), delta=se3.shape[1] == 6)
+        if m.mlp_rt.xyz_encoding_1[0].weight.shape != sd['mlp_rt.xyz_encoding_1.0.weight'].shape:
+            raise ValueError("nerf_root_rts.mlp_rt is not the 8 x 256 head of nerf.py:444-446")
+    elif 'se3' in sd:
+        m = RTExplicit(sd['se3'].shape[0], delta=sd['se3'].shape[1] == 6, rand=False)
+    else:
+        raise NotImplementedError("build_root_pose: no `nerf_root_rts.base_rt.se3` (expmlp) or `nerf_root_rts.se3` (exp) in the "
+                                  "state dict; the `mlp` and `cnn` bases are not rebuilt from checkpoints")
+    m.load_state_dict(sd, strict=True)
+    ks = s.get('ks_param')
+    return {'nerf_root_rts': m.to(device), 'ks_param': None if ks is None else torch.nn.Parameter(ks.to(device))}
+
+
 def build_models(states, device='cuda', data_offset=None, num_freqs=10):
     """states (a MoDA state dict) -> (models, embeddings, extras): `models` / `embeddings` are render_rays' first two
     arguments (moda.py:277-349, 444-465); `extras` holds the per-frame feeders found in the checkpoint

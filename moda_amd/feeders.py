@@ -177,6 +177,203 @@ class DQ_RTHead(NeRF):
         return RtToDqFn.apply(y.reshape(-1, self.num_output)).view(bs, 1, -1)
 
 
+# ---- root (camera) poses: RTHead, RTExplicit, RTExpMLP (nerf.py:307-344, 382-470) on moda_root_pose ----------------------------------
+RAW_NONE, RAW_BASE, RAW_ROWS, RAW_BY_ID = 0, 1, 2, 3          # moda_hip.h MODA_ROOT_RAW_*
+
+
+def _ids(t):
+    """Frame / data ids as the kernels read them: a contiguous device int32 or int64 tensor, and the is-int64 flag."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError("root poses: ids must be a CUDA (ROCm) tensor; the HIP library is the only compute path")
+    if t.dtype not in (torch.int32, torch.int64):
+        t = t.long()
+    return t.reshape(-1).contiguous(), int(t.dtype == torch.int64)
+
+
+def id_rows_sum(rows, ids, T, lanes=0):
+    """The backward of `table[ids]`: (T, C) = sum of rows[i] over ids[i] == t in increasing i (moda_id_rows_sum): no atomics, the
+    same bits on every run and for every `lanes` (lanes per workgroup, 0 = the default)."""
+    r = L.dev(rows)
+    ids, i64 = _ids(ids)
+    if r.dim() != 2 or not 1 <= r.shape[1] <= 8 or ids.shape[0] != r.shape[0]:
+        raise ValueError(f"id_rows_sum: expected rows (n, C <= 8) and n ids, got {tuple(r.shape)} and {ids.shape[0]} ids")
+    out = torch.empty((T, r.shape[1]), device=r.device)
+    L.call("moda_id_rows_sum", L.ptr(r), L.ptr(ids), i64, r.shape[0], T, r.shape[1], L.ptr(out), lanes, L.stream())
+    return out
+
+
+class RootPoseFn(Function):
+    """moda_root_pose: base rows se3[ids] (or None), the MLP's rows `delta` (or None), refine_rt against `rt_raw` and the K row
+    ks[dataid] -> (rtk (n, out_rows, 4), status (4,) int32 = [#frame ids refused, #data ids refused, 0, 0]).  One launch forward;
+    backward one launch plus one deterministic row sum per table (se3, ks)."""
+
+    @staticmethod
+    def forward(ctx, se3, ids, delta, rt_raw, raw_mode, obj_scale, ks, dataid, out_rows):
+        se3 = None if se3 is None else L.dev(se3)
+        delta = None if delta is None else L.dev(delta)
+        rt_raw = None if rt_raw is None else L.dev(rt_raw)
+        ks = None if ks is None else L.dev(ks).reshape(-1, 4)
+        ids, i64 = (None, 0) if ids is None else _ids(ids)
+        dataid, d64 = (None, 0) if dataid is None else _ids(dataid)
+        for t, what in ((se3, "se3"), (delta, "delta")):
+            if t is not None and (t.dim() != 2 or t.shape[1] not in (6, 7)):
+                raise ValueError(f"root poses: {what} must be (rows, 6 | 7), got {tuple(t.shape)}")
+        if rt_raw is not None and (rt_raw.dim() != 3 or rt_raw.shape[1] not in (3, 4) or rt_raw.shape[2] != 4):
+            raise ValueError(f"root poses: rt_raw must be (rows, 3 | 4, 4), got {tuple(rt_raw.shape)}")
+        if (raw_mode in (RAW_ROWS, RAW_BY_ID)) != (rt_raw is not None):
+            raise ValueError("root poses: rt_raw goes with RAW_ROWS / RAW_BY_ID and with nothing else")
+        if delta is None and ids is None:
+            raise ValueError("root poses: neither ids nor delta rows")
+        n = delta.shape[0] if delta is not None else ids.shape[0]
+        for t, what in ((ids, "ids"), (dataid, "dataid")):
+            if t is not None and t.shape[0] != n:
+                raise ValueError(f"root poses: {what} has {t.shape[0]} rows, expected {n}")
+        if raw_mode == RAW_ROWS and rt_raw.shape[0] != n:
+            raise ValueError(f"root poses: rt_raw has {rt_raw.shape[0]} rows, expected {n}")
+        if raw_mode == RAW_BY_ID and se3 is not None and rt_raw.shape[0] != se3.shape[0]:
+            raise ValueError(f"root poses: the rt_raw table has {rt_raw.shape[0]} frames, se3 {se3.shape[0]}")
+        dev = (delta if delta is not None else ids).device
+        T = se3.shape[0] if se3 is not None else (rt_raw.shape[0] if raw_mode == RAW_BY_ID else 0)
+        rtk = torch.empty((n, out_rows, 4), device=dev)
+        status = torch.zeros((4,), device=dev, dtype=torch.int32)
+        ctx.args = (T, 0 if se3 is None else se3.shape[1], i64, n, 0 if delta is None else delta.shape[1], raw_mode,
+                    0 if rt_raw is None else rt_raw.shape[1], float(obj_scale), d64, 0 if ks is None else ks.shape[0], out_rows)
+        ctx.save_for_backward(se3, ids, delta, rt_raw, ks, dataid, status)
+        RootPoseFn._call(ctx.args, se3, ids, delta, rt_raw, ks, dataid, rtk, None, None, None, None, status)
+        ctx.mark_non_differentiable(status)
+        return rtk, status
+
+    @staticmethod
+    def _call(args, se3, ids, delta, rt_raw, ks, dataid, rtk, g, d_rows, d_delta, d_ks, status):
+        T, cols, i64, n, dcols, raw_mode, raw_rows, obj_scale, d64, n_ks, out_rows = args
+        L.call("moda_root_pose", L.ptr(se3), T, cols, L.ptr(ids), i64, n, L.ptr(delta), dcols, L.ptr(rt_raw), raw_mode, raw_rows,
+               obj_scale, L.ptr(ks), L.ptr(dataid), d64, n_ks, out_rows, L.ptr(rtk), L.ptr(g), L.ptr(d_rows), L.ptr(d_delta),
+               L.ptr(d_ks), L.ptr(status), L.stream())
+
+    @staticmethod
+    def backward(ctx, g, _g_status):
+        se3, ids, delta, rt_raw, ks, dataid, status = ctx.saved_tensors
+        n, dev = ctx.args[3], g.device
+        need_ks = ks is not None and ctx.needs_input_grad[6]
+        d_rows = None if se3 is None else torch.empty((n, se3.shape[1]), device=dev)
+        d_delta = None if delta is None else torch.empty_like(delta)
+        d_ks_rows = torch.empty((n, 4), device=dev) if need_ks else None
+        RootPoseFn._call(ctx.args, se3, ids, delta, rt_raw, ks, dataid, None, L.dev(g), d_rows, d_delta, d_ks_rows, status)
+        d_se3 = id_rows_sum(d_rows, ids, se3.shape[0]) if se3 is not None and ctx.needs_input_grad[0] else None
+        d_ks = id_rows_sum(d_ks_rows, dataid, ks.shape[0]) if need_ks else None
+        return d_se3, None, d_delta if ctx.needs_input_grad[2] else None, None, None, None, d_ks, None, None
+
+
+def _rts12(rtk, bs):
+    """(n, 3, 4) -> the reference modules' (bs, 1, 12) = [R (9) | t (3)] (data movement only)."""
+    return torch.cat([rtk[:, :, :3].reshape(-1, 9), rtk[:, :, 3]], -1).view(bs, 1, 12)
+
+
+class RTHead(NeRF):
+    """nerf.py:307-344: code (bs, C) -> rigid transforms (bs, 1, 12) = [R | t]; a quaternion (use_quat) or a rotation vector."""
+
+    def __init__(self, use_quat, **kwargs):
+        super().__init__(**kwargs)
+        self.use_quat = use_quat
+        self.num_output = 7 if use_quat else 6
+        for m in self.modules():
+            if isinstance(m, nn.Linear) and m.bias is not None:
+                m.bias.data.zero_()
+        self.id_status = None
+
+    def raw(self, x):
+        """The MLP's own output rows (n, num_output), before the tail."""
+        return NeRF.forward(self, x).reshape(-1, self.num_output)
+
+    def forward(self, x):
+        rts = self.raw(x)
+        rtk, self.id_status = RootPoseFn.apply(None, None, rts, None, RAW_NONE, 1.0, None, None, 3)
+        return _rts12(rtk, x.shape[0])
+
+
+class RTExplicit(nn.Module):
+    """nerf.py:382-427: frame ids -> rigid transforms (bs, 1, 12) read from the table `se3` (max_t, 7 | 6 with delta)."""
+
+    def __init__(self, max_t, delta=False, rand=True):
+        super().__init__()
+        self.max_t = max_t
+        self.delta = delta
+        trans = torch.zeros(max_t, 3)
+        if delta:
+            rot = torch.zeros(max_t, 3)
+        elif rand:
+            rot = torch.rand(max_t, 4) * 2 - 1
+        else:
+            rot = torch.zeros(max_t, 4)
+            rot[:, 0] = 1
+        se3 = torch.cat([trans, rot], -1)
+        self.se3 = nn.Parameter(se3)
+        self.num_output = se3.shape[-1]
+        self.id_status = None
+
+    def forward(self, x):
+        rtk, self.id_status = RootPoseFn.apply(self.se3, x, None, None, RAW_NONE, 1.0, None, None, 3)
+        return _rts12(rtk, x.shape[0])
+
+
+class FrameCodeTable(FrameCode):
+    """FrameCode whose Fourier coefficients -- a function of the frame id and the video layout alone -- are tabulated once per
+    device for the frames 0 .. max_t - 1 (by FrameCode's own arithmetic, so the code has the same bits) and then gathered: the
+    per-step work is one index_select and the Linear, nothing is read back, and the call can be captured.  The first call on a
+    device builds the table and must therefore happen outside a capture.  The table depends on the constructor's arguments only
+    (max_t, the video layout, scale, the number of frequencies), none of which is a parameter or changes afterwards, so it is never
+    rebuilt.  An id outside [0, max_t) is clamped FOR THE LOOKUP ONLY, so that nothing is read out of bounds; the pose tail that
+    consumes the code refuses the same id (NaN row, counted in its status word), so the clamped code never reaches a result."""
+
+    def __init__(self, max_t, num_freq, embedding_dim, vid_offset, scale=1):
+        super().__init__(num_freq, embedding_dim, vid_offset, scale=scale)
+        self.max_t = max_t
+        self._tables = {}
+
+    def coefficients(self, device):
+        tab = self._tables.get(str(device))
+        if tab is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FrameCodeTable: the coefficient table is built on the first call -- call once before capture")
+            with torch.no_grad():
+                fid = torch.arange(self.max_t, device=device)
+                vid, tid = fid_reindex(fid, self.num_vids, self.vid_offset)
+                coeff = self.fourier_embed(L.dev(tid * self.scale).view(-1, 1))
+                C = coeff.shape[1]
+                wide = torch.zeros((self.max_t, C, self.num_vids), device=device)
+                wide.scatter_(2, L.dev(vid, torch.int64).view(-1, 1, 1).expand(-1, C, 1), coeff[..., None])
+                tab = wide.view(self.max_t, -1).contiguous()
+            self._tables[str(device)] = tab
+        return tab
+
+    def forward(self, fid):
+        tab = self.coefficients(fid.device)
+        # a refused id (outside the table) is clamped for this lookup only: the tail writes NaN for its row and counts it
+        rows = tab.index_select(0, fid.reshape(-1).long().clamp(0, self.max_t - 1))
+        return A.LinearFn.apply(rows, self.basis_mlp.weight, self.basis_mlp.bias, 0)
+
+
+class RTExpMLP(nn.Module):
+    """nerf.py:429-470: the explicit table `base_rt` composed with the MLP delta `mlp_rt(root_code(id))`, the base's gradient
+    magnified 10x.  State-dict keys as the reference's, the `delta_rt.0.*` / `delta_rt.1.*` aliases included."""
+
+    def __init__(self, max_t, num_freqs, t_embed_dim, data_offset, delta=False):
+        super().__init__()
+        self.root_code = FrameCodeTable(max_t, num_freqs, t_embed_dim, data_offset, scale=0.1)
+        self.base_rt = RTExplicit(max_t, delta=delta, rand=False)
+        self.mlp_rt = RTHead(use_quat=False, in_channels_xyz=t_embed_dim, in_channels_dir=0, out_channels=6, raw_feat=True)
+        self.delta_rt = nn.Sequential(self.root_code, self.mlp_rt)
+        self.id_status = None
+
+    def delta_rows(self, x):
+        """The MLP's rows (n, 6) for the frame ids x."""
+        return self.mlp_rt.raw(self.root_code(x))
+
+    def forward(self, x):
+        rtk, self.id_status = RootPoseFn.apply(self.base_rt.se3, x, self.delta_rows(x), None, RAW_NONE, 1.0, None, None, 3)
+        return _rts12(rtk, x.shape[0])
+
+
 def correct_bones(model, bones_rst, inverse=False, neudbs=True):
     """geom_utils.py:933-951: rest bones moved by the rest pose's transforms -> (bones_rst (B,10), bone_rts_rst (1, 8B))."""
     if not neudbs:

@@ -276,6 +276,90 @@ def K2mat(K):
     return Kmat
 
 
+def mat2K(Kmat):
+    """geom_utils.py:612-627: Kmat (...,3,3) -> K (...,4) = fx, fy, px, py."""
+    shape = Kmat.shape[:-2]
+    Kmat = Kmat.view(-1, 3, 3)
+    K = torch.zeros(Kmat.shape[0], 4, device=Kmat.device)
+    K[:, 0] = Kmat[:, 0, 0]
+    K[:, 1] = Kmat[:, 1, 1]
+    K[:, 2] = Kmat[:, 0, 2]
+    K[:, 3] = Kmat[:, 1, 2]
+    return K.view(shape + (4,))
+
+
+def K2inv(K):
+    """geom_utils.py:638-652: K (...,4) -> the inverse intrinsics matrix (bs,3,3), in quotients (1 / fx, -px / fx)."""
+    K = K.view(-1, 4)
+    bs = K.shape[0]
+    Kmat = torch.zeros(bs, 3, 3, device=K.device)
+    Kmat[:, 0, 0] = 1. / K[:, 0]
+    Kmat[:, 1, 1] = 1. / K[:, 1]
+    Kmat[:, 0, 2] = -K[:, 2] / K[:, 0]
+    Kmat[:, 1, 2] = -K[:, 3] / K[:, 1]
+    Kmat[:, 2, 2] = 1
+    return Kmat
+
+
+def Kmatinv(Kmat):
+    """geom_utils.py:629-636: the inverse of an intrinsics matrix (...,3,3) through mat2K and K2inv."""
+    return K2inv(mat2K(Kmat)).view(Kmat.shape)
+
+
+def create_base_se3(bs, device):
+    """moda.py:1025-1033: (bs,3,4) identity rotations at t = (0, 0, 0.3)."""
+    rt = torch.zeros(bs, 3, 4, device=device)
+    rt[:, 0, 0] = rt[:, 1, 1] = rt[:, 2, 2] = 1.
+    rt[:, 2, 3] = 0.3
+    return rt
+
+
+def refine_rt(rt_raw, root_rts):
+    """moda.py:1450-1466: the initial poses rt_raw (bs, 3|4, 4) composed with the delta root_rts (bs,1,12) = [R | t]; a copy.
+    The stand-alone helper, plain torch on device tensors; compute_rts / convert_root_pose (moda_amd.root_pose) run this inside
+    moda_root_pose."""
+    rt_raw = rt_raw.clone()
+    root_rmat = root_rts[:, 0, :9].view(-1, 3, 3)
+    root_tmat = root_rts[:, 0, 9:12]
+    rmat = rt_raw[:, :3, :3].clone()
+    tmat = rt_raw[:, :3, 3].clone()
+    tmat = tmat + rmat.matmul(root_tmat[..., None])[..., 0]
+    rmat = rmat.matmul(root_rmat)
+    rt_raw[:, :3, :3] = rmat
+    rt_raw[:, :3, 3] = tmat
+    return rt_raw
+
+
+class RayCamsFn(torch.autograd.Function):
+    """moda_ray_cams: rtk (n,4,4), kaug (n,4) -> Rmat, Tmat, Kinv; the backward reaches every row of rtk, its K row included."""
+
+    @staticmethod
+    def forward(ctx, rtk, kaug):
+        r, k = L.dev(rtk), L.dev(kaug)
+        n = r.shape[0]
+        R, T, Ki = (torch.empty(s, device=r.device) for s in ((n, 3, 3), (n, 3), (n, 3, 3)))
+        L.call("moda_ray_cams", L.ptr(r), L.ptr(k), n, L.ptr(R), L.ptr(T), L.ptr(Ki), None, None, None, None, L.stream())
+        ctx.save_for_backward(r, k)
+        return R, T, Ki
+
+    @staticmethod
+    def backward(ctx, gR, gT, gK):
+        r, k = ctx.saved_tensors
+        d = torch.empty_like(r)
+        gR, gT, gK = (None if g is None else L.dev(g) for g in (gR, gT, gK))
+        L.call("moda_ray_cams", L.ptr(r), L.ptr(k), r.shape[0], None, None, None, L.ptr(gR), L.ptr(gT), L.ptr(gK), L.ptr(d),
+               L.stream())
+        return d, None
+
+
+def prepare_ray_cams(rtk, kaug):
+    """moda.py:1036-1046: rtk (bs,4,4), kaug (bs,4) -> Rmat (bs,3,3), Tmat (bs,3), Kinv (bs,3,3) = Kmatinv(K2inv(kaug) @
+    K2mat(rtk[:, 3])); one launch each way."""
+    if rtk.dim() != 3 or tuple(rtk.shape[1:]) != (4, 4) or kaug.reshape(-1, 4).shape[0] != rtk.shape[0]:
+        raise ValueError(f"prepare_ray_cams: expected rtk (bs,4,4) and kaug (bs,4), got {tuple(rtk.shape)} and {tuple(kaug.shape)}")
+    return RayCamsFn.apply(rtk, kaug.reshape(-1, 4))
+
+
 def pinhole_cam(in_verts, K):
     """geom_utils.py:654-673: verts (...,N,3), K (...,4) -> (x / (1e-6 + z), y / (1e-6 + z), z) after the intrinsics."""
     verts = in_verts.clone()

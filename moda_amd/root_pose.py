@@ -1,0 +1,65 @@
+"""The root (camera) poses of a training step, device-resident: `compute_rts` (reference nnutils/moda.py:1468-1495) gives the pose
+table of all frames that the root-smoothness term reads (loss_utils.forward_loss(rtk_all=...)), `convert_root_pose`
+(moda.py:1419-1447) the batch's (bs,4,4) poses with their intrinsics row, which geom_utils.prepare_ray_cams turns into what
+feeders.raycast takes.  The reference's methods read their inputs off the model object; here they are arguments.
+
+Whatever the module -- RTExpMLP (`expmlp`, the default), RTExplicit (`exp`), nn.Sequential(code, RTHead) (`mlp`) -- its tail,
+refine_rt / create_base_se3 and the K row are ONE launch of moda_root_pose; the (bs,1,12) intermediate of the reference is not
+formed.  An id outside the table does not raise as the reference's indexing would: its row is NaN and it is counted in
+`nerf_root_rts.id_status` (device int32 [#frame ids refused, #data ids refused, 0, 0]; nothing is read back here)."""
+import torch
+from torch import nn
+
+from .feeders import RAW_BASE, RAW_ROWS, FrameCode, RootPoseFn, RTExplicit, RTExpMLP, RTHead
+
+
+def _parts(nerf_root_rts, frameid):
+    """-> (se3 table | None, delta rows | None) of a root-pose module for the frame ids."""
+    m = nerf_root_rts
+    if isinstance(m, RTExpMLP):
+        return m.base_rt.se3, m.delta_rows(frameid)
+    if isinstance(m, RTExplicit):
+        return m.se3, None
+    if isinstance(m, nn.Sequential) and len(m) == 2 and isinstance(m[1], RTHead):
+        if not isinstance(m[0], (nn.Embedding, FrameCode)):      # anything else would be handed frame ids it cannot take
+            raise NotImplementedError(f"root poses: the `mlp` basis is nn.Sequential(nn.Embedding | FrameCode, RTHead); a first stage "
+                                      f"{type(m[0]).__name__} -- root_basis='cnn', the pose CNN `Encoder` over image features "
+                                      "(moda.py:367-373) -- is not implemented")
+        return None, m[1].raw(m[0](frameid))
+    if isinstance(m, RTHead):
+        return None, m.raw(frameid)
+    raise NotImplementedError(f"root poses: {type(m).__name__} is not a root-pose module (RTExpMLP, RTExplicit, Sequential(code, "
+                              "RTHead)); root_basis='cnn' needs the pose CNN `Encoder`, which is not implemented")
+
+
+def _tail(nerf_root_rts, frameid, rt_raw, obj_scale, ks, dataid, out_rows, root_opt):
+    se3, delta = _parts(nerf_root_rts, frameid) if root_opt else (None, None)
+    mode = RAW_BASE if rt_raw is None else RAW_ROWS
+    rtk, status = RootPoseFn.apply(se3, frameid, delta, rt_raw, mode, obj_scale if rt_raw is not None else 1.0, ks, dataid, out_rows)
+    if nerf_root_rts is not None:
+        nerf_root_rts.id_status = status
+    return rtk
+
+
+def compute_rts(nerf_root_rts, num_fr, *, rt_raw=None, obj_scale=1.0, root_opt=True):
+    """moda.py:1468-1495 -> (num_fr,3,4), the current poses of all frames.  rt_raw (num_fr, 3|4, 4): the initial poses of a
+    dataset with cameras (use_cam; their translation is divided by obj_scale); None: create_base_se3."""
+    dev = next(nerf_root_rts.parameters()).device if nerf_root_rts is not None else rt_raw.device
+    return _tail(nerf_root_rts, _arange(int(num_fr), dev), rt_raw, obj_scale, None, None, 3, root_opt)
+
+
+_ARANGE = {}
+
+
+def _arange(n, device):
+    """Frame ids 0 .. n - 1, built once per (n, device): no host-to-device work inside a step or a capture."""
+    k = (n, str(device))
+    if k not in _ARANGE:
+        _ARANGE[k] = torch.arange(n, device=device, dtype=torch.int64)
+    return _ARANGE[k]
+
+
+def convert_root_pose(nerf_root_rts, frameid, dataid, ks_param, *, rtk=None, obj_scale=1.0, root_opt=True):
+    """moda.py:1419-1447 -> (bs,4,4): the poses of the batch's frames with row 3 = ks_param[dataid].  rtk (bs, 3|4, 4): the
+    dataset's initial poses (use_cam), not modified; None: create_base_se3."""
+    return _tail(nerf_root_rts, frameid, rtk, obj_scale, ks_param, dataid, 4, root_opt)
