@@ -29,7 +29,8 @@ extern "C" {
 #define MODA_EINVAL (-1)   /* unsupported / inconsistent argument */
 #define MODA_ESHAPE (-2)   /* shape outside what the kernels were instantiated for */
 
-/* ABI version; bumped on any signature change.  10: the two older loss-sum entries left (both are moda_loss_assembly). */
+/* ABI version; bumped on any signature change.  10: the two older loss-sum entries left (both are moda_loss_assembly).
+ * Still 11 with moda_adamw_step: a purely additive entry changes no signature. */
 int moda_abi_version(void);
 
 /* 0 when `stream` is not being captured into a HIP graph, else the runtime's id of that capture (hipStreamGetCaptureInfo): a
@@ -961,6 +962,43 @@ int moda_id_rows_sum(const float* rows, const void* ids, int32_t ids64, int64_t 
  * included; kaug gets no gradient. */
 int moda_ray_cams(const float* rtk, const float* kaug, int64_t n, float* Rmat, float* Tmat, float* Kinv, const float* g_Rmat,
                   const float* g_Tmat, const float* g_Kinv, float* d_rtk, void* stream);
+
+/* ------------------------------------------------------------------------
+ * The optimiser step (moda_amd/csrc/optim_kernels.hip; a purely additive entry: no existing signature changed, so
+ * moda_abi_version() stays 11).  Reads nothing back and allocates nothing: it may run on a capturing stream, and a replayed
+ * graph follows the learning-rate schedule, because the step counter lives on the device.
+ * ------------------------------------------------------------------------ */
+#define MODA_OPTIM_MAX_GROUPS 64
+
+/* moda_adamw_step: torch.optim.AdamW (decoupled weight decay, no amsgrad) over parameter groups driven by
+ * torch.optim.lr_scheduler.OneCycleLR (two phases, anneal_strategy 'linear', cycle_momentum False), as the reference's trainer
+ * builds them (nnutils/train_utils.py:226-290) and steps them (:967-969), in two launches.  Every table is DEVICE memory.
+ * Segments (n_seg): one per parameter tensor that HAS a gradient.  seg_p[s] / seg_g[s] the fp32 parameter and its gradient
+ * (contiguous, 4-byte aligned; float4 accesses where a chunk start is 16-byte aligned), seg_numel[s] >= 1, seg_group[s] in 0..G-1,
+ * seg_moff[s] the offset of the segment's moments in exp_avg / exp_avg_sq (n_state floats each).  Chunks as for moda_clip_grad:
+ * chunk c covers [chunk_off[c], min(chunk_off[c] + MODA_CLIP_CHUNK, numel)) of segment chunk_seg[c], in any order.  A chunk whose
+ * entries do not describe a range of a segment and of the state buffers is skipped, never followed.
+ * Schedule: max_lr[g] float64, G <= MODA_OPTIM_MAX_GROUPS.  With t = step[0] (int64, 0 before the first step) the step applies
+ * OneCycleLR's rate at t -- initial = max / div_factor, min = initial / final_div_factor, phase ends pct_start * total_steps - 1 and
+ * total_steps - 1, (end - start) * pct + start, all in float64 in torch's operations, for every t <= total_steps (its slight
+ * extrapolation at t == total_steps included).  t > total_steps, where torch raises: the rate of total_steps is held and
+ * status[0] (int32[4], zeroed by the caller once) is incremented (saturating).  lr (2 G fp32): lr[g] = the rate applied,
+ * lr[G + g] = the rate at min(t + 1, total_steps), which is what param_groups[g]['lr'] holds after scheduler.step().  step[0]
+ * becomes t + 1.
+ * Per segment: k = ++seg_step[s] (int64; torch keeps `step` per parameter, and a parameter without a gradient does not step),
+ * seg_fac[3 s ..] = (float)(1 - lr * weight_decay), (float)(lr / (1 - beta1^k)), (float)sqrt(1 - beta2^k), each computed in
+ * float64 and rounded once.  Per element, each operation rounded to fp32, divide and square root correctly rounded:
+ *   p *= f0;  m += (float)(1 - beta1) * (g - m);  v *= (float)beta2;  v += ((float)(1 - beta2) * g) * g;
+ *   p -= (f1 * m) / (sqrt(v) / f2 + (float)eps);   zero_grad != 0: g = 0 afterwards (literal zeros).
+ * The gradients are used as they are: zeros (a rejected or frozen step of moda_clip_grad) still decay and step, as in torch.
+ * MODA_EINVAL: G outside 1..MODA_OPTIM_MAX_GROUPS, total_steps < 1, pct_start outside [0, 1], a schedule phase of zero length
+ * (torch divides by zero there), a factor or beta out of range, a missing table.  n_chunks == 0 still advances the counters. */
+int moda_adamw_step(float* const* seg_p, float* const* seg_g, const int64_t* seg_numel, const int32_t* seg_group,
+                    const int64_t* seg_moff, int32_t n_seg, const int32_t* chunk_seg, const int64_t* chunk_off, int32_t n_chunks,
+                    const double* max_lr, int32_t G, int64_t total_steps, double pct_start, double div_factor,
+                    double final_div_factor, double beta1, double beta2, double eps, double weight_decay, int64_t* step,
+                    int64_t* seg_step, float* exp_avg, float* exp_avg_sq, int64_t n_state, float* lr, float* seg_fac,
+                    int32_t* status, int32_t zero_grad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -37,3 +37,5 @@ from .feeders import RTHead, RTExplicit, RTExpMLP, id_rows_sum  # noqa: F401
 from .geom_utils import K2mat, K2inv, Kmatinv, mat2K, refine_rt, create_base_se3, prepare_ray_cams  # noqa: F401
 from . import root_pose  # noqa: F401
 from .root_pose import compute_rts, convert_root_pose  # noqa: F401
+from . import optim  # noqa: F401
+from .optim import DeviceAdamW, build_optimizer, optimizer_step, group_lr_factors  # noqa: F401

@@ -152,6 +152,9 @@ _SIGNATURES = {
     "moda_root_pose": (_c.c_int, [_P, _I64, _I32, _P, _I32, _I64, _P, _I32, _P, _I32, _I32, _F32, _P, _P, _I32, _I64, _I32] + [_P] * 7),
     "moda_id_rows_sum": (_c.c_int, [_P, _P, _I32, _I64, _I64, _I32, _P, _I32, _P]),
     "moda_ray_cams": (_c.c_int, [_P, _P, _I64] + [_P] * 8),
+    # the optimiser step: OneCycleLR + AdamW over parameter groups (optim_kernels.hip): an additive entry, the ABI stays 11
+    "moda_adamw_step": (_c.c_int, [_P] * 5 + [_I32, _P, _P, _I32, _P, _I32, _I64] + [_c.c_double] * 7 + [_P] * 4 + [_I64, _P, _P, _P,
+                                                                                                              _I32, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -95,7 +95,8 @@ class TrainHarness:
 
     def __init__(self, N=2048, S=128, B=25, precision="bf16", rank=0, world=1, dist=None, lr=2e-5, device=None, seed=1000,
                  rays_per_frame=4, fused_adamw=True, bucket=True, use_fine=False, with_unc=False, strong=False, clip_grad=False,
-                 clip_scale=10.0, default_losses=False, bone_loc=False, root_pose=False):
+                 clip_scale=10.0, default_losses=False, bone_loc=False, root_pose=False, device_optimizer=False, total_steps=None,
+                 num_epochs=None):
         """use_fine / with_unc: the reference's LAST training stage (scripts/template.sh:59: --fine_steps 0 --use_unc): S/2 coarse
         depths rendered without gradients (rendering.py:91-107, here on the fused inference kernels in `PREPASS_PRECISION[precision]`),
         S/2 importance samples merged in, and the uncertainty network nerf_unc (8x256, moda.py:457-464) trained on
@@ -115,7 +116,12 @@ class TrainHarness:
         root_pose (with default_losses): the reference's default root poses (moda.py:83-85: root_opt, root_basis 'expmlp', no
         cameras) inside the step -- an RTExpMLP over this harness's frames, one video [0, n_frames), weights from synth; every step
         calls root_pose.compute_rts and the loss runs with root_sm=True on that table; the module's parameters join the optimiser,
-        the gradient bucket and the clipper's names (`nerf_root_rts.*`).  The rays stay the synthetic ones.  Off by default."""
+        the gradient bucket and the clipper's names (`nerf_root_rts.*`).  The rays stay the synthetic ones.  Off by default.
+        device_optimizer: the reference's optimiser and schedule (train_utils.py:226-290) on the device -- moda_amd.optim.DeviceAdamW
+        over named_params(): 22 groups, OneCycleLR peaking at `lr` x the group's factor after 2 of `num_epochs` epochs, over
+        `total_steps` steps -- in place of the constant-rate torch AdamW, in eager_step and in every capture form; a replayed graph
+        follows the schedule.  `opt` is None then and `dev_opt` the optimiser; every parameter must belong to a group.  Off by
+        default: the benchmarked step and every other path are unchanged."""
         from moda_amd import sharding
         global DEV
         # strong=True: ONE batch of N rays (the one-rank run's rays) cut into contiguous per-rank ranges (sharding.shard_rays), so
@@ -177,13 +183,20 @@ class TrainHarness:
         self.loss_buf = torch.zeros(2, device=self.dev)
         self.terms = torch.zeros(len(TRAIN_TERMS), device=self.dev)
         kw = dict(lr=lr, betas=(0.9, 0.999), weight_decay=1e-4, capturable=True)
-        self.opt = None
-        if fused_adamw:     # one fused kernel per step (the foreach form issues ~150 one-element divisions for its bias corrections)
+        self.opt = self.dev_opt = None
+        if device_optimizer:
+            from moda_amd.optim import DeviceAdamW
+            if total_steps is None or num_epochs is None:
+                raise ValueError("TrainHarness: device_optimizer=True needs the schedule's total_steps and num_epochs")
+            self.dev_opt = DeviceAdamW(self.named_params(), lr, total_steps, 2. / num_epochs, root_basis="expmlp")
+            if self.dev_opt.skipped:
+                raise ValueError(f"TrainHarness: parameters without an optimiser group: {self.dev_opt.skipped}")
+        elif fused_adamw:     # one fused kernel per step (the foreach form issues ~150 one-element divisions for its bias corrections)
             try:
                 self.opt = torch.optim.AdamW(self.params, fused=True, **kw)
             except (RuntimeError, TypeError, ValueError):
                 self.opt = None
-        if self.opt is None:
+        if self.opt is None and self.dev_opt is None:
             self.opt = torch.optim.AdamW(self.params, **kw)
         self.gen = torch.Generator(device=self.dev)
         self.gen.manual_seed(seed * 7919 + rank)
@@ -251,6 +264,13 @@ class TrainHarness:
             self.clipper = GradClipper(self.named_params(), self.clip_scale)
         self.clipper()
 
+    def _opt_step(self):
+        """The optimiser stage: torch's AdamW at a constant rate, or the device optimiser and its schedule (two launches)."""
+        if self.dev_opt is not None:
+            self.dev_opt.step()
+        else:
+            self.opt.step()
+
     @staticmethod
     def _masked_mean(x, m):            # x[m].mean() without the boolean gather (no host sync, graph-capturable)
         m = m.to(x.dtype).expand_as(x)
@@ -314,7 +334,11 @@ class TrainHarness:
     def zero_grad(self):
         """Every gradient gone: the bucket by one memset (recorded into a captured graph like any launch), the rest set to None."""
         if self.bucket is None:
-            self.opt.zero_grad(set_to_none=True)
+            if self.opt is not None:
+                self.opt.zero_grad(set_to_none=True)
+            else:
+                for p in self.params:
+                    p.grad = None
             return
         inb = {id(p) for p in self.bucket.params}
         for p in self.params:
@@ -356,7 +380,7 @@ class TrainHarness:
             sharding.allreduce_gradients(self.params, self.dist, self.world)
             sharding.allreduce_sums(self.loss_buf, self.dist, self.world)
         self._clip()
-        self.opt.step()
+        self._opt_step()
         self.steps_done += 1
         return self.loss_buf
 
@@ -405,7 +429,7 @@ class TrainHarness:
             with torch.cuda.graph(graph):
                 body()
                 self._clip()
-                self.opt.step()
+                self._opt_step()
             self.graph, self.graph_tail, self.graph_form = graph, None, "one graph"
             return graph
         if self.bucket is None:
@@ -416,7 +440,7 @@ class TrainHarness:
                 body()
                 self.bucket.all_reduce(self.dist, self.world, force=True)
                 self._clip()
-                self.opt.step()
+                self._opt_step()
             self.graph, self.graph_tail, self.graph_form = graph, None, "one graph with the all-reduce inside"
             return graph
         head, tail = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -425,7 +449,7 @@ class TrainHarness:
         with torch.cuda.graph(tail, capture_error_mode="thread_local"):
             self.bucket.scale(self.world)
             self._clip()
-            self.opt.step()
+            self._opt_step()
         self.graph, self.graph_tail, self.graph_form = head, tail, "two graphs around one eager all-reduce"
         # the captures themselves execute nothing: parameters and optimiser state are those after `warm` steps
         return head
