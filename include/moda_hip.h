@@ -1000,6 +1000,57 @@ int moda_adamw_step(float* const* seg_p, float* const* seg_g, const int64_t* seg
                     int64_t* seg_step, float* exp_avg, float* exp_avg_sq, int64_t n_state, float* lr, float* seg_fac,
                     int32_t* status, int32_t zero_grad, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Pixel sampling of a training step, banmo.sample_pxs (nnutils/moda.py:1048-1260; moda_amd/csrc/pixsample_kernels.hip; purely
+ * additive entries: no existing signature changed, so moda_abi_version() stays 11).  Nothing allocates, synchronises or reads
+ * back, every launch goes to `stream`, so the stage can be captured.  No float atomics; the same bits on every run.
+ * ------------------------------------------------------------------------ */
+#define MODA_TOPK_MAX_N 65536              /* longest row of moda_topk_rows (the cost is n^2 compares a row) */
+
+/* moda_topk_rows: values (rows, n) fp32 -> idx_out (rows, k) int32 and val_out (rows, k)|NULL, the k first elements of every row
+ * under the total order
+ *   key = the value with -0 taken as +0 and every NaN taken as ONE key above +inf;  descending key, then ascending index.
+ * (torch.topk ranks NaN highest too and leaves ties unspecified.)  val_out holds the values as stored (a -0 stays -0).  status[0]
+ * += the number of NaNs in `values` (int32, zeroed by the caller).  The pair (key, index) is unique, so an element's rank -- the
+ * number of pairs ordered before it -- is a permutation: every lane counts its element's rank while the row streams through LDS
+ * and writes idx_out[rank] when rank < k.  No sort, no atomics on the outputs, no LDS bound on n.  Rows of n <= 256 share a
+ * workgroup (256 / n rows each); longer rows take ceil(n / 256) workgroups each.
+ * MODA_ESHAPE (before any pointer is looked at): n < 1, n > MODA_TOPK_MAX_N, rows < 0, rows * n >= 2^31, rows > 65535 with
+ * n > 256.  MODA_EINVAL: k < 1, k > n, a NULL pointer. */
+int moda_topk_rows(const float* values, int64_t rows, int64_t n, int64_t k, int32_t* idx_out, float* val_out, int32_t* status,
+                   void* stream);
+
+/* moda_pxs_assemble: the split / topk-select / stack / cat / view(-1) sequence of moda.py:1075-1191 in one launch, one thread a
+ * ray.  rand_inds (bs, 5 nsample) int64: nsample uniform draws, then the 4 nsample candidates.  n_u uniform and n_s active rays
+ * per line / frame (n_s == 0: active sampling off, topk unused).  The id arrays (bs,) are int32, or int64 where ids64.
+ * Line mode (line_mode != 0, bs even, P = bs / 2, lines b = h P + l, K = n_s P, topk (K,) int32 indices into the first half's
+ * (P, 4 nsample) candidates): half h owns rays h (P n_u + K) + ...; first the P n_u uniform rays (l, j < n_u), column
+ * rand_inds[b, j]; then the K active rays t, c = topk[t], l = c / (4 nsample), j = c % (4 nsample), column
+ * rand_inds[b, nsample + j] -- the same c for both halves.  Outputs, R = 2 (P n_u + K) rays: rand_out (R,) int64, xys_out (R, 2)
+ * = (column, lineid[b]), frameid / frameid_sub / dataid / errid / batch_map (= b) (R,) int64, near_far_out (R, 2) =
+ * near_far[frameid].
+ * Frame mode: topk (bs, n_s) per-row indices into the row's 4 nsample candidates; R = bs (n_u + n_s); rand_out / xys_out per ray
+ * (x = ind % img_size, y = ind / img_size), the id outputs and near_far_out per FRAME (bs rows).
+ * Refused, never followed, nothing raises: a column outside [0, img_size) (frame mode: [0, img_size^2)) or a topk entry outside
+ * its range gives a NaN xys row and status[2] += 1; a frame id outside [0, n_frames) gives a NaN near_far row, a data id outside
+ * [0, n_vid) (n_vid == 0: unchecked) is only counted, each status[1] += 1 per written row.  status: 4 int32 zeroed by the caller =
+ * [#NaN predictions (moda_topk_rows), #ids refused, #columns refused, 0]. */
+int moda_pxs_assemble(const int64_t* rand_inds, int64_t bs, int32_t nsample, int32_t n_u, int32_t n_s, int32_t line_mode,
+                      int64_t img_size, const void* lineid, const void* frameid, const void* frameid_sub, const void* dataid,
+                      const void* errid, int32_t ids64, const int32_t* topk, const float* near_far, int64_t n_frames, int64_t n_vid,
+                      int64_t* rand_out, float* xys_out, int64_t* frameid_out, int64_t* frameid_sub_out, int64_t* dataid_out,
+                      int64_t* errid_out, int64_t* batch_map_out, float* near_far_out, int32_t* status, void* stream);
+
+/* moda_obs_gather: obs_to_rays_line / obs_to_rays (moda.py:1215-1260) in one launch, one thread per (ray, channel), without
+ * forming t[batch_map]: imgs (B,3,W), masks, vis2d, occ (B,1,W), flow (B,2,W), dp_feats (B,16,W)|NULL; ray r reads row
+ * batch_map[r] (NULL: r / ns) at column cols[r] (both int64) -> img_at (R,3), sil_at, vis_at, cfd_at (R,1), flo_at (R,2),
+ * feats_at (R,16).  A row outside [0, B) or a column outside [0, W) is not followed: the ray's values are NaN, and with status
+ * != NULL status[1] / status[2] count them. */
+int moda_obs_gather(const float* imgs, const float* masks, const float* vis2d, const float* flow, const float* occ,
+                    const float* dp_feats, int64_t B, int64_t W, const int64_t* batch_map, const int64_t* cols, int64_t R, int64_t ns,
+                    float* img_at, float* sil_at, float* vis_at, float* flo_at, float* cfd_at, float* feats_at, int32_t* status,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,3 +39,5 @@ from . import root_pose  # noqa: F401
 from .root_pose import compute_rts, convert_root_pose  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import DeviceAdamW, build_optimizer, optimizer_step, group_lr_factors  # noqa: F401
+from . import pixel_sampling  # noqa: F401
+from .pixel_sampling import sample_pxs, topk_rows, gather_obs, unc_ray_inputs  # noqa: F401

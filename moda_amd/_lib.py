@@ -155,6 +155,10 @@ _SIGNATURES = {
     # the optimiser step: OneCycleLR + AdamW over parameter groups (optim_kernels.hip): an additive entry, the ABI stays 11
     "moda_adamw_step": (_c.c_int, [_P] * 5 + [_I32, _P, _P, _I32, _P, _I32, _I64] + [_c.c_double] * 7 + [_P] * 4 + [_I64, _P, _P, _P,
                                                                                                               _I32, _P]),
+    # pixel sampling: top-k under a total order, ray assembly, observation gather (pixsample_kernels.hip): additive, the ABI stays 11
+    "moda_topk_rows": (_c.c_int, [_P, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "moda_pxs_assemble": (_c.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I64] + [_P] * 5 + [_I32, _P, _P, _I64, _I64] + [_P] * 10),
+    "moda_obs_gather": (_c.c_int, [_P] * 6 + [_I64, _I64, _P, _P, _I64, _I64] + [_P] * 8),
 }
 
 EXPORTS = tuple(_SIGNATURES)
