@@ -1051,6 +1051,50 @@ int moda_obs_gather(const float* imgs, const float* masks, const float* vis2d, c
                     float* img_at, float* sil_at, float* vis_at, float* flo_at, float* cfd_at, float* feats_at, int32_t* status,
                     void* stream);
 
+/* ------------------------------------------------------------------------
+ * The per-frame tables of a training run: banmo.save_latest_vars (nnutils/moda.py:1497-1513), the near-far reset of
+ * forward_default (:485-491) and get_near_far (nnutils/geom_utils.py:1105-1135) (moda_amd/csrc/frames_kernels.hip; purely
+ * additive entries: no existing signature changed, so moda_abi_version() stays 11).  Nothing allocates, synchronises or reads
+ * back, every launch goes to `stream`, so the chain compute_rts -> near_far -> rays can be captured.  No float atomics; a table
+ * row has one writer and min / max do not depend on arrival order: the same bits on every run.  status: 4 int32 zeroed by the
+ * caller once = [#frames given a NaN plane, #frame ids refused, 0, 0].
+ * ------------------------------------------------------------------------ */
+#define MODA_NEAR_FAR_MAX_SPLIT 256        /* most point ranges a frame of moda_near_far is cut into */
+#define MODA_FRAMES_MAX_BATCH 65536        /* longest batch of moda_frames_scatter (an entry scans the entries after it) */
+
+/* moda_frames_scatter: rtk (bs,4,4), kaug (bs,4), rt_raw (bs,3,4) fp32 and frameid (bs,) int64 into the tables tab_rtk (M,4,4),
+ * tab_rt_raw (M,3,4), tab_idk (M,) fp32.  Rows 0-2 of rtk and rt_raw are copied bit for bit, tab_idk[f] = 1, and row 3 becomes
+ * mat2K(K2inv(kaug) @ K2mat(rtk[3])) in the reference's operations, each rounded to fp32 and never contracted:
+ *   a = 1 / kaug0, b = 1 / kaug1, c = -kaug2 / kaug0, d = -kaug3 / kaug1;
+ *   row 3 = (a fx + 0 + c 0, 0 + b fy + d 0, a px + 0 py + c, 0 px + b py + d), each sum left to right.
+ * A frame named several times keeps its LAST occurrence in batch order, as numpy's fancy assignment does: entry b writes only
+ * if no entry after it names the same frame, so every row has exactly one writer.  An id outside [0, M) is not written and
+ * status[1] += 1.  MODA_ESHAPE: bs < 0, bs > MODA_FRAMES_MAX_BATCH, M < 1, M >= 2^27.  MODA_EINVAL: a NULL pointer. */
+int moda_frames_scatter(const float* rtk, const float* kaug, const float* rt_raw, const int64_t* frameid, int64_t bs,
+                        float* tab_rtk, float* tab_rt_raw, float* tab_idk, int64_t M, int32_t* status, void* stream);
+
+/* moda_near_far: get_near_far over pts (N,3) fp32 and the tables tab_rtk (M,4,4), idk (M,), near_far (M,2) (in place).
+ * rtk_all (M,3,4)|NULL: the pose patch of moda.py:486-488 first -- rows 0-2 of every frame with idk != 0 (numpy's astype(bool):
+ * a NaN counts) are replaced by rtk_all's, in the table too; row 3 is kept.  Per frame with idk == 1 (an exact compare), with
+ * R, T the frame's (patched) pose and every operation rounded to fp32, never contracted:
+ *   x, y, z = ((p0 R[i][0] + p1 R[i][1]) + p2 R[i][2]) + T[i];  depth = (x 0 + y 0) + z   (pinhole_cam's product with K2mat^T:
+ *   z for finite x and y, NaN otherwise, as in the reference);
+ *   pmin, pmax over the points;  delta = (pmax - pmin) * (float)(tol_fac - 1.0);
+ *   near = max(pmin - delta, 1e-3f), far = max(pmax + delta, 1e-3f), NaN kept as torch.clamp keeps it.
+ * A NaN depth gives the frame two NaN planes (a flag is carried beside fminf / fmaxf); a frame given a NaN plane adds 1 to
+ * status[0].  Every other row of near_far keeps its bits.
+ * Launch: N <= 32 (the per-step reset's 8 box corners): one lane a frame, ceil(M / 64) workgroups.  Otherwise one 256-lane
+ * workgroup per (frame, point range), lanes striding the range, waves reduced by shuffles and joined in LDS.  splits == 0
+ * chooses the number of ranges, moda_near_far_splits(N, M) = clamp(min(ceil(1024 / M), ceil(N / 4096)), 1,
+ * MODA_NEAR_FAR_MAX_SPLIT) (1 for N <= 32): the points are split only when M alone gives fewer than 4 workgroups a CU.
+ * splits > 0 forces that many (at most N).  With more than one range the workgroups leave (min, max, NaN flag) in
+ * ws (M * splits * 3 floats, caller's) and a second small kernel, one lane a frame, folds them and writes the planes -- no
+ * atomics on the way.  MODA_ESHAPE: N < 1, M < 1, 3 N or 16 M >= 2^31.  MODA_EINVAL: splits outside 0..MODA_NEAR_FAR_MAX_SPLIT,
+ * splits > 1 with N <= 32 or without ws, a NULL pointer. */
+int32_t moda_near_far_splits(int64_t N, int64_t M);
+int moda_near_far(const float* pts, int64_t N, float* tab_rtk, const float* idk, float* near_far, int64_t M, double tol_fac,
+                  const float* rtk_all, int32_t splits, float* ws, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

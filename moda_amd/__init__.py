@@ -41,3 +41,6 @@ from . import optim  # noqa: F401
 from .optim import DeviceAdamW, build_optimizer, optimizer_step, group_lr_factors  # noqa: F401
 from . import pixel_sampling  # noqa: F401
 from .pixel_sampling import sample_pxs, topk_rows, gather_obs, unc_ray_inputs  # noqa: F401
+from . import frame_state  # noqa: F401
+from .frame_state import (FrameState, save_latest_vars, get_near_far, reset_near_far, near_far_to_bound, reset_nf,  # noqa: F401
+                          reset_obj_bound)

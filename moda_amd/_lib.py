@@ -159,6 +159,10 @@ _SIGNATURES = {
     "moda_topk_rows": (_c.c_int, [_P, _I64, _I64, _I64, _P, _P, _P, _P]),
     "moda_pxs_assemble": (_c.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I64] + [_P] * 5 + [_I32, _P, _P, _I64, _I64] + [_P] * 10),
     "moda_obs_gather": (_c.c_int, [_P] * 6 + [_I64, _I64, _P, _P, _I64, _I64] + [_P] * 8),
+    # frame tables: save_latest_vars, get_near_far with the pose patch (frames_kernels.hip): additive, the ABI stays 11
+    "moda_frames_scatter": (_c.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P]),
+    "moda_near_far_splits": (_I32, [_I64, _I64]),
+    "moda_near_far": (_c.c_int, [_P, _I64, _P, _P, _P, _I64, _c.c_double, _P, _I32, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -96,7 +96,7 @@ class TrainHarness:
     def __init__(self, N=2048, S=128, B=25, precision="bf16", rank=0, world=1, dist=None, lr=2e-5, device=None, seed=1000,
                  rays_per_frame=4, fused_adamw=True, bucket=True, use_fine=False, with_unc=False, strong=False, clip_grad=False,
                  clip_scale=10.0, default_losses=False, bone_loc=False, root_pose=False, device_optimizer=False, total_steps=None,
-                 num_epochs=None):
+                 num_epochs=None, nf_reset=False):
         """use_fine / with_unc: the reference's LAST training stage (scripts/template.sh:59: --fine_steps 0 --use_unc): S/2 coarse
         depths rendered without gradients (rendering.py:91-107, here on the fused inference kernels in `PREPASS_PRECISION[precision]`),
         S/2 importance samples merged in, and the uncertainty network nerf_unc (8x256, moda.py:457-464) trained on
@@ -121,9 +121,17 @@ class TrainHarness:
         over named_params(): 22 groups, OneCycleLR peaking at `lr` x the group's factor after 2 of `num_epochs` epochs, over
         `total_steps` steps -- in place of the constant-rate torch AdamW, in eager_step and in every capture form; a replayed graph
         follows the schedule.  `opt` is None then and `dev_opt` the optimiser; every parameter must belong to a group.  Off by
-        default: the benchmarked step and every other path are unchanged."""
+        default: the benchmarked step and every other path are unchanged.
+        nf_reset (with root_pose): the near-far reset of forward_default (moda.py:485-491, every step once progress >= nf_reset:
+        the recipe's last stage) inside the step, right after compute_rts, in eager mode and in every capture form --
+        moda_amd.reset_near_far on `frames`, a FrameState over this harness's frames, all marked seen, with the box of
+        synth.make_rest_mesh's bounds for a rest mesh; `near_far` is its (n_frames, 2) table.  The harness's rays stay the
+        synthetic ones, so the table is produced in the reference's position and NOT consumed.  Off by default: the harness has
+        no `frames` then, and the benchmarked step and every other path are unchanged."""
         from moda_amd import sharding
         global DEV
+        if nf_reset and not root_pose:
+            raise ValueError("TrainHarness: nf_reset=True recomputes the planes from the root poses of compute_rts (root_pose=True)")
         # strong=True: ONE batch of N rays (the one-rank run's rays) cut into contiguous per-rank ranges (sharding.shard_rays), so
         # that the union of the ranks' rays is the single-rank batch; default: every rank owns its own N rays (weak, DDP's lines)
         n_total = N
@@ -178,6 +186,17 @@ class TrainHarness:
             self.data_offset = (0, self.n_frames)
             self.root_rts = make_root_rts(self.n_frames, self.data_offset).to(self.dev).train()
             self.params += list(self.root_rts.parameters())
+        self.frames = self.near_far = None
+        if nf_reset:
+            from moda_amd.frame_state import FrameState
+            from moda_amd.mesh import TriMesh
+            v, f = synth.make_rest_mesh()
+            self.near_far = torch.zeros((self.n_frames, 2), device=self.dev)
+            self.frames = self.latest_vars = FrameState(self.n_frames, self.dev, self.near_far)
+            self.frames.mesh_rest = TriMesh(torch.from_numpy(v).to(self.dev), torch.from_numpy(f).to(self.dev))
+            self.frames.idk.fill_(1.0)
+            self.frames.rtk[:, 3] = torch.tensor([1.0, 1.0, 0.0, 0.0], device=self.dev)
+            self.frames.box()                                           # the 8 corners go up here, not inside a step
         self.opts = make_opts(dist_corresp=True, use_corresp=True, use_ot=True)
         self.bound = np.asarray([0.2, 0.2, 0.2], np.float32)
         self.loss_buf = torch.zeros(2, device=self.dev)
@@ -321,6 +340,9 @@ class TrainHarness:
         if self.root_pose:                                             # moda.py:667-670 over compute_rts (moda.py:1468-1495)
             from moda_amd.root_pose import compute_rts
             rtk_all = compute_rts(self.root_rts, self.n_frames)
+            if self.frames is not None:                                # moda.py:485-491, one launch, nothing read back
+                from moda_amd.frame_state import reset_near_far
+                reset_near_far(self, rtk_all.detach())
         loss, aux = forward_loss(r, self.loss_opts, loss_filter=self.loss_filter, errid=self.errid, frameid=self.frameid, progress=1.0,
                                  bone_loc=bone_loc, rtk_all=rtk_all, data_offset=self.data_offset if self.root_pose else None)
         loss.backward()
