@@ -356,18 +356,22 @@ class WarpFn(Function):
         cyc = torch.empty((N, S), device=p.device) if cr is not None else None
         L.call("moda_warp_prepped_fwd", L.ptr(pr), per_ray, L.ptr(qq), L.ptr(p), L.ptr(pt), L.ptr(ds), 0, L.ptr(aux), N, S, B,
                L.ptr(out), L.ptr(skin), L.ptr(cr), L.ptr(cyc), L.stream())
-        ctx.save_for_backward(pr, qq, p, skin, aux, cr, pt)
+        ctx.save_for_backward(pr, qq, p, skin, aux, cr, pt, cyc)
         ctx.per_ray = per_ray
         ctx.has_dskin = ds is not None
         return out, cyc, skin
 
     @staticmethod
     def backward(ctx, g_out, g_cyc, g_skin):
-        pr, qq, p, skin, aux, cr, pt = ctx.saved_tensors
+        pr, qq, p, skin, aux, cr, pt, cyc = ctx.saved_tensors
         N, S, _ = p.shape
         B = qq.shape[1]
         dev = p.device
         c = lambda t: None if t is None else _f32(t)
+        if cr is not None and g_cyc is not None:
+            # |ref - out| has gradient 0 where it IS 0.  The kernel recomputes out from the saved weights, an ulp off the
+            # forward's, so where the forward returned 0 its residual is a unit vector of rounding noise: drop those samples here
+            g_cyc = torch.where(cyc == 0, torch.zeros_like(cyc), c(g_cyc))
         d_p = torch.empty_like(p)
         d_pt = torch.empty_like(p) if pt is not None else None
         d_ds = torch.empty((N, S, B), device=dev)
