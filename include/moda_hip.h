@@ -1095,6 +1095,65 @@ int32_t moda_near_far_splits(int64_t N, int64_t M);
 int moda_near_far(const float* pts, int64_t N, float* tab_rtk, const float* idk, float* near_far, int64_t M, double tol_fac,
                   const float* rtk_all, int32_t splits, float* ws, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------
+ * DensePose-CSE matching: ood_check_cse (nnutils/geom_utils.py:1610-1663), resample_dp / bbox_dp2rnd (:1665-1701),
+ * compute_flow_cse / match2flo (:1207-1247) (moda_amd/csrc/cse_kernels.hip; purely additive entries: no existing signature
+ * changed, so moda_abi_version() stays 11).  fp32.  Nothing allocates, synchronises or reads back, every launch goes to `stream`,
+ * so the calls can be captured.  No float atomics: the same bits on every run.
+ * ------------------------------------------------------------------------ */
+#define MODA_CSE_CHANNELS 16         /* the only feature width the arg-max is built for */
+#define MODA_CSE_QUERY_TILE 128      /* queries per workgroup (4 waves x 32) */
+#define MODA_CSE_CAND_TILE 256       /* candidates per LDS tile; the ranges of a split are whole tiles */
+#define MODA_OOD_MAX_BLOCKS 64       /* partials of moda_ood_error: B * MODA_OOD_MAX_BLOCKS * 2 doubles */
+#define MODA_RESAMPLE_GRID 0         /* explicit affine, F.grid_sample's convention */
+#define MODA_RESAMPLE_DP 1           /* resample_dp: the affine from dp_bbox and kaug, the branch test in the kernel */
+#define MODA_RESAMPLE_INTERP 2       /* F.interpolate(mode='bilinear', align_corners=False) */
+
+/* moda_feat_argmax: idx[b][i] (int32) = the candidate j in [0, M) with the largest score
+ *   s = fma(q15, c15, ... fma(q1, c1, fma(q0, c0, 0))), the fp32 chain in ascending k, each step rounded once
+ * (v_mfma_f32_32x32x2_f32 computes exactly this chain).  Element (b, row, k) of the queries is q[b q_sb + row q_sr + k q_sk]
+ * (q_sb = 0: one set of queries for every batch element), of the candidates c[b c_sb + row c_sr + k c_sk]: (rows, 16) tables and
+ * (16, h, w) images are both read in place.  Order: the larger score wins; of equal scores the lowest j; a NaN score beats
+ * every number and the lowest NaN j wins (torch.argmax); -0 == +0.
+ * Candidates are cut into `splits` ranges of whole tiles when B * ceil(N / MODA_CSE_QUERY_TILE) workgroups are too few:
+ * splits == 0 lets the library choose (towards 1024 workgroups), splits > 0 forces that many (at most the number of tiles);
+ * moda_feat_argmax_splits returns the number of ranges actually used and their length for either.  With more than one range,
+ * keys (B * N uint64, caller's workspace; NULL: one range) receives, by atomicMax, (order(s) << 32) | (0xFFFFFFFF - j) with
+ * order() the score's bits mapped to an unsigned integer that rises with the score (NaN on top), and a second small kernel
+ * unpacks idx: the result has the same bits for every split and on every run.
+ * MODA_ESHAPE: B < 1, M < 1, N < 0, B N >= 2^31, M >= 2^31 - 256.  MODA_EINVAL: a NULL pointer, splits < 0.  N == 0: nothing. */
+int32_t moda_feat_argmax_splits(int64_t B, int64_t N, int64_t M, int32_t forced, int64_t* range);
+int moda_feat_argmax(const float* q, int64_t q_sb, int64_t q_sr, int64_t q_sk, const float* c, int64_t c_sb, int64_t c_sr,
+                     int64_t c_sk, int64_t B, int64_t N, int64_t M, int32_t splits, int32_t* idx, uint64_t* keys, void* stream);
+
+/* moda_grid_resample: src (B,C,Hs,Ws) -> dst (B,C,Hd,Wd), bilinear, one launch.  Every operation rounded to fp32, never
+ * contracted.  For destination pixel (x, y):
+ *   MODA_RESAMPLE_INTERP: fx = max((Ws / Wd) (x + 0.5) - 0.5, 0), likewise fy; the neighbours are clamped to the edge.
+ *   MODA_RESAMPLE_GRID:   affine (B,6) = (r00, r10, t0, r01, r11, t1): u = (x r00 + y r10) + t0, v = (x r01 + y r11) + t1;
+ *                         gx = u / Ws * 2 - 1, gy = v / Ws * 2 - 1 (the reference divides both by the width);
+ *                         fx = ((gx + 1) Ws - 1) / 2, fy = ((gy + 1) Hs - 1) / 2; neighbours outside the image read 0, and a
+ *                         pixel whose (fx, fy) is outside (-1, Ws) x (-1, Hs) or not a number is 0.
+ *   MODA_RESAMPLE_DP:     if every one of the 4 B values of dp_bbox is +-0 (dp_bbox.abs().sum() == 0, tested by every
+ *                         workgroup): as INTERP.  Otherwise as GRID with, from dp_bbox (B,4) and kaug (B,4),
+ *                         sx = (b2 - b0) / 112, sy = (b3 - b1) / 112, m00 = (1 / k0) sx, m02 = (1 / k0) b0 + (-k2 / k0),
+ *                         r00 = 1 / m00, t0 = -m02 / m00, likewise m11, m12, r11, t1 from (sy, b1, k1, k3); r10 = r01 = 0.
+ *   x0 = floor(fx), w1 = fx - x0, w0 = 1 - w1 per axis; value = (v00 wx0 + v01 wx1) wy0 + (v10 wx0 + v11 wx1) wy1.
+ * normalize != 0: every pixel's C values are divided by max(sqrt(sum of squares in ascending c), 1e-12) (F.normalize).
+ * MODA_ESHAPE: a size < 1, B C Hs Ws or B C Hd Wd >= 2^31, B >= 2^24.  MODA_EINVAL: a NULL pointer the mode needs, another mode. */
+int moda_grid_resample(const float* src, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hd, int64_t Wd, int32_t mode,
+                       const float* affine, const float* dp_bbox, const float* kaug, int32_t normalize, float* dst, void* stream);
+
+/* moda_ood_error: the forward-backward check of ood_check_cse.  idx (B,N) int32: per frame the pixel (of an h x w image) matched
+ * to each embedding row; dp_idx (B,Hi,Wi) int32, reduced to (h, w) by torch's `nearest` rule, source = min(floor(dst * (in / out)),
+ * in - 1) with the scale in fp32.  Per frame: the mean over the pixels p = (x, y) with d = dp_idx[p] != 0 of
+ * sqrtf(dx dx + dy dy), (dx, dy) = (m % w - x, m / w - y), m = idx[d]; the terms are added in float64 (per-thread partials, a
+ * shuffle / LDS tree, workgroup partials in index order), the mean is rounded to fp32 -> error (B,), and
+ * valid (B,) uint8 = error < threshold.  No pixel: NaN and 0.  A d outside [0, N) (or an idx value outside [0, h w)) is not read
+ * through, contributes nothing and adds 1 to status[0] (int32, zeroed by the caller; NULL: not counted).
+ * partials: B * MODA_OOD_MAX_BLOCKS * 2 doubles, caller's.  MODA_ESHAPE: a size < 1, B N or B Hi Wi >= 2^31, h w >= 2^30. */
+int moda_ood_error(const int32_t* idx, const int32_t* dp_idx, int64_t B, int64_t N, int64_t h, int64_t w, int64_t Hi, int64_t Wi,
+                   float threshold, double* partials, float* error, uint8_t* valid, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,3 +44,6 @@ from .pixel_sampling import sample_pxs, topk_rows, gather_obs, unc_ray_inputs  #
 from . import frame_state  # noqa: F401
 from .frame_state import (FrameState, save_latest_vars, get_near_far, reset_near_far, near_far_to_bound, reset_nf,  # noqa: F401
                           reset_obj_bound)
+from . import cse  # noqa: F401
+from .cse import (bbox_dp2rnd, resample_dp, ood_check_cse, feat_argmax, match2coords, match2flo,  # noqa: F401
+                  compute_flow_cse)

@@ -163,6 +163,11 @@ _SIGNATURES = {
     "moda_frames_scatter": (_c.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P]),
     "moda_near_far_splits": (_I32, [_I64, _I64]),
     "moda_near_far": (_c.c_int, [_P, _I64, _P, _P, _P, _I64, _c.c_double, _P, _I32, _P, _P, _P]),
+    # DensePose-CSE matching: feature arg-max, affine bilinear resample, reprojection error (cse_kernels.hip): additive, the ABI stays 11
+    "moda_feat_argmax_splits": (_I32, [_I64, _I64, _I64, _I32, _c.POINTER(_I64)]),
+    "moda_feat_argmax": (_c.c_int, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P, _P, _P]),
+    "moda_grid_resample": (_c.c_int, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _P]),
+    "moda_ood_error": (_c.c_int, [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _F32, _P, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
