@@ -1154,6 +1154,65 @@ int moda_grid_resample(const float* src, int64_t B, int64_t C, int64_t Hs, int64
 int moda_ood_error(const int32_t* idx, const int32_t* dp_idx, int64_t B, int64_t N, int64_t h, int64_t w, int64_t Hi, int64_t Wi,
                    float threshold, double* partials, float* error, uint8_t* valid, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Frame-pair preparation: compute_crop_params, the cv2.remap calls of read_raw, flow_process / warp_flow
+ * (dataloader/vidbase.py:142-246), convert_batch_input's pair-major order (nnutils/moda.py:1362-1417)
+ * (moda_amd/csrc/framepair_kernels.hip; purely additive entries of ABI 11: no existing signature changed, so
+ * moda_abi_version() stays 11).  fp32 data, float64 coordinates, nothing contracted.  Nothing allocates, synchronises or reads
+ * back, every launch goes to `stream`, so the calls can be captured.  No float atomics: the same bits on every run.
+ *
+ * The sampler restates cv2.remap with float maps and the default constant-zero border:
+ *   MODA_REMAP_LINEAR   sx = rne(x * 32) (the product in fp32, round half to even), cell x0 = sx >> 5, fraction f = sx & 31,
+ *                       likewise sy, y0, g.  Weights w00 = (1 - g/32)(1 - f/32), w01 = (1 - g/32)(f/32), w10 = (g/32)(1 - f/32),
+ *                       w11 = (g/32)(f/32), exact in fp32.  value = ((v00 w00 + v01 w01) + v10 w10) + v11 w11 with v00 at
+ *                       (x0, y0), v01 at (x0 + 1, y0), v10 at (x0, y0 + 1), v11 at (x0 + 1, y0 + 1); a tap outside the image is 0.
+ *   MODA_REMAP_NEAREST  the pixel (rne(x), rne(y)); 0 outside the image.
+ * A coordinate that is NaN, infinite or of magnitude >= 2^25 (linear) / 2^30 (nearest) is outside every image: the value is 0.
+ * Frames are at most 32767 pixels a side.
+ * ------------------------------------------------------------------------ */
+#define MODA_REMAP_NEAREST 0         /* cv2.INTER_NEAREST */
+#define MODA_REMAP_LINEAR 1          /* cv2.INTER_LINEAR */
+
+/* moda_mask_bbox: masks (B,h,w), fp32 (is_u8 == 0) or uint8, the object wherever the value is > 0 (NaN is not) ->
+ * box (B,4) int32 = xmin, xmax, ymin, ymax.  An empty mask gives (w, -1, h, -1).  Wave reduction, then integer atomicMin / atomicMax.
+ * MODA_ESHAPE: a size < 1, h or w >= 32768, B >= 65536. */
+int moda_mask_bbox(const void* masks, int32_t is_u8, int64_t B, int64_t h, int64_t w, int32_t* box, void* stream);
+
+/* moda_crop_params: compute_crop_params per frame.  box (B,4) as above.  cx = (xmax + xmin) / 2, lx = (xmax - xmin) / 2 in integers,
+ * Lx = (int)(crop_factor * (double)lx) (toward zero), alp0 = (double)(2 Lx) / img_size, tx = cx - Lx; likewise y.
+ * affine (B,4) float64 = alp0, alp1, tx, ty; kaug (B,4) fp32 = the same four values rounded.  bs > 0 (B == 2 bs): frame
+ * f = 2 pair + k of the input is written to row k bs + pair (pair-major, convert_batch_input); bs == 0: row f.
+ * An empty box adds 1 to status[0], a box with Lx == 0 or Ly == 0 adds 1 to status[1] (int32 x 2, zeroed by the caller; NULL:
+ * not counted); such a frame's rows are NaN, and moda_crop_remap / moda_flow_process write zeros for it without reading through.
+ * MODA_ESHAPE: B < 1, B >= 65536, img_size outside 1..16384, bs > 0 with B != 2 bs.  MODA_EINVAL: NULL, crop_factor outside (0, 1024). */
+int moda_crop_params(const int32_t* box, int64_t B, int64_t bs, int64_t img_size, double crop_factor, float* kaug, double* affine,
+                     int32_t* status, void* stream);
+
+/* moda_crop_remap: the crop of every plane of B frames to img_size x img_size, one thread per output pixel.  The source coordinate
+ * is x = (float)((double)col * alp0 + tx), y = (float)((double)row * alp1 + ty): one float64 multiply and one add, each rounded,
+ * then the rounding to fp32.  affine (B,4) is in OUTPUT order; output row o reads input frame f = 2 (o % bs) + o / bs (bs > 0) or
+ * f = o.  Inputs (NULL with its output NULL: skipped): img (B,h,w,3) uint8, each tap divided by 255 in fp32, linear; flow (B,h,w,2)
+ * fp32, linear; occ (B,h,w) fp32, linear; mask (B,h,w) fp32 / uint8 (mask_u8), nearest, then > 0; dp (B,h,w) int32, nearest.
+ * Outputs, fp32: o_img (B,3,S,S), o_flow (B,2,S,S), o_occ, o_mask, o_dp, o_vis (B,S,S); o_vis is 1 where the nearest sample is
+ * inside the frame and o_mask is (mask * vis) > 0.  MODA_ESHAPE as above; MODA_EINVAL: an output without its input, affine NULL. */
+int moda_crop_remap(const uint8_t* img, const float* flow, const float* occ, const void* mask, int32_t mask_u8, const int32_t* dp,
+                    const double* affine, int64_t B, int64_t bs, int64_t h, int64_t w, int64_t img_size, float* o_img, float* o_flow,
+                    float* o_occ, float* o_mask, float* o_dp, float* o_vis, void* stream);
+
+/* moda_flow_process: flow_process for bs pairs in one launch.  flow_c (2 bs,2,S,S): the cropped flows in pixels of the source
+ * frame, pair-major (row p and row bs + p are a pair); affine (2 bs,4) in the same order.  For row o with partner q, pixel (c, r):
+ *   hx = c alp0[o] + tx[o];  fx = (float)(((flow_c + hx) - tx[q]) / alp0[q] - c)   (float64 inside; likewise y),
+ * the closed form of the reference's product with inv(A B) of the partner.  The forward-backward check samples, by the linear
+ * rule above at the fp32 map (fx + c, fy + r), the image whose pixel (xi, yi) is (xi, yi) + the partner's flow re-expressed the same
+ * way (recomputed at each tap; a tap outside is the constant 0), blended in float64; dis = |sample - (c, r)|,
+ * occ = exp(-25 (dis / S * 2)), 0 when < 0.25; flow = 2 (fx / S) in fp32.  A NaN affine row in the pair: zeros for both rows.
+ * MODA_ESHAPE: bs < 1, bs >= 32768, img_size outside 1..16384.  MODA_EINVAL: NULL, flow == flow_c. */
+int moda_flow_process(const float* flow_c, const double* affine, int64_t bs, int64_t img_size, float* flow, float* occ, void* stream);
+
+/* moda_remap: src (C,Hs,Ws) fp32 planes sampled at map_x, map_y (H,W) fp32 -> dst (C,H,W), by the rule `interpolation` above. */
+int moda_remap(const float* src, int64_t C, int64_t Hs, int64_t Ws, const float* map_x, const float* map_y, int64_t H, int64_t W,
+               int32_t interpolation, float* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,3 +47,6 @@ from .frame_state import (FrameState, save_latest_vars, get_near_far, reset_near
 from . import cse  # noqa: F401
 from .cse import (bbox_dp2rnd, resample_dp, ood_check_cse, feat_argmax, match2coords, match2flo,  # noqa: F401
                   compute_flow_cse)
+from . import frame_pairs  # noqa: F401
+from .frame_pairs import (mask_bbox, compute_crop_params, remap, warp_flow, crop_frames, flow_process,  # noqa: F401
+                          fb_flow_check, prepare_frame_pairs)

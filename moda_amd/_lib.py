@@ -168,6 +168,12 @@ _SIGNATURES = {
     "moda_feat_argmax": (_c.c_int, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P, _P, _P]),
     "moda_grid_resample": (_c.c_int, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _P]),
     "moda_ood_error": (_c.c_int, [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _F32, _P, _P, _P, _P, _P]),
+    # frame-pair preparation: mask box, crop parameters, crop remap, flow_process, remap (framepair_kernels.hip): additive, the ABI stays 11
+    "moda_mask_bbox": (_c.c_int, [_P, _I32, _I64, _I64, _I64, _P, _P]),
+    "moda_crop_params": (_c.c_int, [_P, _I64, _I64, _I64, _c.c_double, _P, _P, _P, _P]),
+    "moda_crop_remap": (_c.c_int, [_P, _P, _P, _P, _I32, _P, _P, _I64, _I64, _I64, _I64, _I64] + [_P] * 7),
+    "moda_flow_process": (_c.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
+    "moda_remap": (_c.c_int, [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I32, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
