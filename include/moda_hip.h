@@ -1213,6 +1213,64 @@ int moda_flow_process(const float* flow_c, const double* affine, int64_t bs, int
 int moda_remap(const float* src, int64_t C, int64_t Hs, int64_t Ws, const float* map_x, const float* map_y, int64_t H, int64_t W,
                int32_t interpolation, float* dst, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Warm-up stages: shape_init_loss, rtk_loss, compute_root_sm_loss (nnutils/loss_utils.py:540-572, :151-163, :520-537) and the
+ * rotation preset of train() (nnutils/train_utils.py:662-666)
+ * (moda_amd/csrc/warmup_kernels.hip; purely additive entries of ABI 11: no existing signature changed, so
+ * moda_abi_version() stays 11).  fp32 data, nothing contracted.  Nothing allocates, synchronises or reads back, every launch goes
+ * to `stream`, and every scalar a backward needs is read from device memory, so the calls can be captured.  No float atomics: the
+ * same bits on every run.
+ *
+ * Poses are rows of 4 floats: rtk (T, rows, 4) with rows 3 or 4, contiguous and 16-byte aligned; R = [:, :3, :3], t = [:, :3, 3].
+ * A gradient buffer has the shape of its input; row 3 of a (T,4,4) input gets zeros.  T < 2^24.
+ * rot_angle(X Y^T) = acosf(clamp((tr - 1) / 2, (float)(-1 + 1e-4), (float)(1 - 1e-4))), tr the sum over i = 0, 1, 2 of
+ * (X[i][0] Y[i][0] + X[i][1] Y[i][1]) + X[i][2] Y[i][2]; its gradient is 0 outside the bounds and passes AT them (torch's clamp).
+ * ------------------------------------------------------------------------ */
+#define MODA_SHAPE_LOSS_MAX_BLOCKS 1024   /* doubles in the `partials` buffer of the shape-loss forward */
+
+/* moda_shape_target: the sample points and SDF targets of shape_init_loss in one launch.  u (N,3) uniforms in [0, 1),
+ * obj_bound (3) on the device, b = obj_bound * bound_factor.  pts (N,3) = (u * 2) * b - b, three separately rounded fp32
+ * operations (bit-equal to the reference on the same u).  dis (N): ellips != 0: (sqrt((q0 q0 + q1 q1) + q2 q2) - 1) * mean with
+ * q_k = pts_k / obj_bound_k and mean = ((o0 + o1) + o2) / 3; ellips == 0: sqrt((p0 p0 + p1 p1) + p2 p2) - min(obj_bound).  Divide
+ * and square root correctly rounded.  MODA_ESHAPE: N < 1, 3 N >= 2^31.  MODA_EINVAL: a NULL pointer, pts == u. */
+int moda_shape_target(const float* u, int64_t N, const float* obj_bound, float bound_factor, int32_t ellips, float* pts, float* dis,
+                      void* stream);
+
+/* moda_shape_loss_fwd: loss[0] = mean over i of r_i r_i, r_i = -y_i - dis_i (the square rounded to fp32, the sum in float64: each
+ * of min(ceil(N / 256), MODA_SHAPE_LOSS_MAX_BLOCKS) workgroups sums its grid-strided elements -- per lane in index order, lanes by
+ * the xor butterfly 32..1, waves in order -- into partials[block]; a second launch sums the partials the same way).  Two launches.
+ * moda_shape_loss_bwd: dy_i = -((g[0] / N) * (2 r_i)), g on the device.  dy_sum (1), optional: the sum of the fp32 dy_i in float64
+ * by the same tree (two more launches; `partials` as above), rounded once -- the gradient of a bias that is added directly in front
+ * of y, with the same bits on every run.  MODA_ESHAPE: N < 1, N >= 2^31.  MODA_EINVAL: NULL, dy_sum without partials. */
+int moda_shape_loss_fwd(const float* y, const float* dis, int64_t N, double* partials, float* loss, void* stream);
+int moda_shape_loss_bwd(const float* y, const float* dis, int64_t N, const float* g, float* dy, double* partials, float* dy_sum,
+                        void* stream);
+
+/* moda_rtk_loss_fwd: rtk_loss over T frames, one workgroup.  out3 = [rot_loss + trn_loss, rot_loss = 0.01 mean rot_angle(Rp Rg^T),
+ * trn_loss = mean |tp - tg|^2]; the per-frame terms are fp32, their sums float64.
+ * moda_rtk_loss_bwd: drtk (the shape of rtk) for the gradients g_total, g_rot, g_trn of the three outputs (device scalars; a NULL
+ * one counts as zero).  One thread per frame, no reduction. */
+int moda_rtk_loss_fwd(const float* rtk, int32_t rows, const float* rtk_gt, int32_t rows_gt, int64_t T, float* out3, void* stream);
+int moda_rtk_loss_bwd(const float* rtk, int32_t rows, const float* rtk_gt, int32_t rows_gt, int64_t T, const float* g_total,
+                      const float* g_rot, const float* g_trn, float* drtk, void* stream);
+
+/* moda_root_sm1_fwd: compute_root_sm_loss.  offsets (n_videos + 1) int32: video v holds the frames [offsets[v], offsets[v + 1]);
+ * its pairs are (i, i + 1) with both frames inside it, so a video of fewer than two frames has none.  The pairs of all videos are
+ * pooled: out4 = [loss, 1e-3 mean rot_angle(R_i R_{i+1}^T), 0.1 mean |t_i - t_{i+1}|, #pairs]; no pair at all: NaN, NaN, NaN, 0.
+ * moda_root_sm1_bwd: drtk for the gradient g[0] of out4[0] (device scalar; out4 as the forward left it).  One thread per frame
+ * gathers its pair as first frame, then its pair as second frame; the norm's gradient at a zero difference is 0. */
+int moda_root_sm1_fwd(const float* rtk, int32_t rows, int64_t T, const int32_t* offsets, int32_t n_videos, float* out4, void* stream);
+int moda_root_sm1_bwd(const float* rtk, int32_t rows, int64_t T, const int32_t* offsets, int32_t n_videos, const float* out4,
+                      const float* g, float* drtk, void* stream);
+
+/* moda_matrix_to_quat: T rotation matrices, matrix i at R + i mat_stride with rows row_stride floats apart, -> quat (T,4) unit
+ * quaternions, real part first and >= 0.  With d = (1 + r00 + r11 + r22, 1 + r00 - r11 - r22, 1 - r00 + r11 - r22,
+ * 1 - r00 - r11 + r22) = 4 q_k^2, the largest d_k (a tie: the lowest k) picks the row of
+ *   (d0, r21 - r12, r02 - r20, r10 - r01), (r21 - r12, d1, r01 + r10, r02 + r20),
+ *   (r02 - r20, r01 + r10, d2, r12 + r21), (r10 - r01, r02 + r20, r12 + r21, d3)
+ * which is divided by its norm and negated when its first entry is negative.  MODA_ESHAPE: T < 1, T >= 2^31. */
+int moda_matrix_to_quat(const float* R, int64_t T, int64_t mat_stride, int64_t row_stride, float* quat, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

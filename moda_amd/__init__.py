@@ -50,3 +50,7 @@ from .cse import (bbox_dp2rnd, resample_dp, ood_check_cse, feat_argmax, match2co
 from . import frame_pairs  # noqa: F401
 from .frame_pairs import (mask_bbox, compute_crop_params, remap, warp_flow, crop_frames, flow_process,  # noqa: F401
                           fb_flow_check, prepare_frame_pairs)
+from .loss_utils import shape_init_loss, rtk_loss, compute_root_sm_loss, compute_root_sm_2nd_loss  # noqa: F401
+from .geom_utils import matrix_to_quaternion  # noqa: F401
+from . import warmup  # noqa: F401
+from .warmup import forward_warmup_shape, forward_warmup_rootmlp, preset_root_rotations, WarmupHarness  # noqa: F401

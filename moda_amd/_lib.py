@@ -174,6 +174,15 @@ _SIGNATURES = {
     "moda_crop_remap": (_c.c_int, [_P, _P, _P, _P, _I32, _P, _P, _I64, _I64, _I64, _I64, _I64] + [_P] * 7),
     "moda_flow_process": (_c.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
     "moda_remap": (_c.c_int, [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I32, _P, _P]),
+    # warm-up stages: shape_init_loss, rtk_loss, compute_root_sm_loss, matrix_to_quaternion (warmup_kernels.hip): additive, the ABI stays 11
+    "moda_shape_target": (_c.c_int, [_P, _I64, _P, _F32, _I32, _P, _P, _P]),
+    "moda_shape_loss_fwd": (_c.c_int, [_P, _P, _I64, _P, _P, _P]),
+    "moda_shape_loss_bwd": (_c.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P]),
+    "moda_rtk_loss_fwd": (_c.c_int, [_P, _I32, _P, _I32, _I64, _P, _P]),
+    "moda_rtk_loss_bwd": (_c.c_int, [_P, _I32, _P, _I32, _I64, _P, _P, _P, _P, _P]),
+    "moda_root_sm1_fwd": (_c.c_int, [_P, _I32, _I64, _P, _I32, _P, _P]),
+    "moda_root_sm1_bwd": (_c.c_int, [_P, _I32, _I64, _P, _I32, _P, _P, _P, _P]),
+    "moda_matrix_to_quat": (_c.c_int, [_P, _I64, _I64, _I64, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1279,3 +1279,88 @@ class SinkhornDivFn(Function):
     def backward(ctx, g):
         gx, gy = ctx.saved_tensors
         return (gx * g if ctx.needs_input_grad[0] else None), (gy * g if gy is not None else None), None, None, None, None
+
+
+SHAPE_LOSS_MAX_BLOCKS = 1024        # moda_hip.h MODA_SHAPE_LOSS_MAX_BLOCKS
+
+
+class ShapeLossFn(Function):
+    """shape_init_loss' last two lines (loss_utils.py:570-571): mean((-y - dis)^2) over y (N,) | (N,1) and the targets dis (N,)
+    (moda_shape_loss_fwd / _bwd: block partials in float64 summed in index order; the backward reads the incoming gradient from
+    device memory).  -> the loss, a 0-dim tensor.  No gradient flows to dis.
+    dy_sum (1,), optional: a device buffer the BACKWARD fills with sum(dy) formed by the same fixed tree -- the gradient of a bias
+    added directly in front of y (NeRF's sigma.bias), which the network's own backward forms with float atomics."""
+
+    @staticmethod
+    def forward(ctx, y, dis, dy_sum=None):
+        ys, ds = _f32(y).reshape(-1), _f32(dis).reshape(-1)
+        if ys.numel() != ds.numel() or ys.numel() < 1:
+            raise ValueError(f"shape loss: y holds {ys.numel()} values, dis {ds.numel()}")
+        if dy_sum is not None and not (dy_sum.is_cuda and dy_sum.dtype == torch.float32 and dy_sum.numel() == 1):
+            raise ValueError("dy_sum: expected an fp32 device tensor of one element")
+        partials = torch.empty((SHAPE_LOSS_MAX_BLOCKS,), device=ys.device, dtype=torch.float64)
+        loss = torch.empty((1,), device=ys.device)
+        L.call("moda_shape_loss_fwd", L.ptr(ys), L.ptr(ds), ys.numel(), L.ptr(partials), L.ptr(loss), L.stream())
+        ctx.save_for_backward(ys, ds)
+        ctx.shape, ctx.dy_sum = y.shape, dy_sum
+        return loss.reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        ys, ds = ctx.saved_tensors
+        dy = torch.empty_like(ys)
+        partials = None if ctx.dy_sum is None else torch.empty((SHAPE_LOSS_MAX_BLOCKS,), device=ys.device, dtype=torch.float64)
+        L.call("moda_shape_loss_bwd", L.ptr(ys), L.ptr(ds), ys.numel(), L.ptr(_f32(g).reshape(1)), L.ptr(dy), L.ptr(partials),
+               L.ptr(ctx.dy_sum), L.stream())
+        return dy.view(ctx.shape), None, None
+
+
+class RtkLossFn(Function):
+    """rtk_loss (loss_utils.py:151-163) over the predicted rtk (T, 3 | 4, 4) and the table rtk_raw (T, 3 | 4, 4): one kernel
+    forward, one backward with one thread per frame (moda_rtk_loss_fwd / _bwd).  -> (total, rot_loss, trn_loss), 0-dim views of
+    one device buffer, each differentiable with respect to rtk (the warm-up stage weights rot_loss on its own)."""
+
+    @staticmethod
+    def forward(ctx, rtk, rtk_raw):
+        r, gt = _f32(rtk), _f32(rtk_raw)
+        out = torch.empty((3,), device=r.device)
+        L.call("moda_rtk_loss_fwd", L.ptr(r), r.shape[1], L.ptr(gt), gt.shape[1], r.shape[0], L.ptr(out), L.stream())
+        ctx.save_for_backward(r, gt)
+        ctx.set_materialize_grads(False)
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_total, g_rot, g_trn):
+        r, gt = ctx.saved_tensors
+        gs = [None if g is None else _f32(g).reshape(1) for g in (g_total, g_rot, g_trn)]
+        d = torch.empty_like(r)
+        L.call("moda_rtk_loss_bwd", L.ptr(r), r.shape[1], L.ptr(gt), gt.shape[1], r.shape[0], L.ptr(gs[0]), L.ptr(gs[1]), L.ptr(gs[2]),
+               L.ptr(d), L.stream())
+        return d, None
+
+
+class RootSm1Fn(Function):
+    """compute_root_sm_loss (loss_utils.py:520-537) over rtk (T, 3 | 4, 4) and the device table of video offsets (V + 1,) int32:
+    one kernel forward, one gather kernel backward (moda_root_sm1_fwd / _bwd).  -> (loss 0-dim, parts (3,) detached =
+    [1e-3 mean angle, 0.1 mean trn, #pairs])."""
+
+    @staticmethod
+    def forward(ctx, rtk, offsets):
+        r = _f32(rtk)
+        out = torch.empty((4,), device=r.device)
+        L.call("moda_root_sm1_fwd", L.ptr(r), r.shape[1], r.shape[0], L.ptr(offsets), offsets.numel() - 1, L.ptr(out), L.stream())
+        ctx.save_for_backward(r, offsets, out)
+        parts = out[1:]
+        ctx.mark_non_differentiable(parts)
+        return out[0], parts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_parts):
+        r, offsets, out = ctx.saved_tensors
+        d = torch.empty_like(r)
+        L.call("moda_root_sm1_bwd", L.ptr(r), r.shape[1], r.shape[0], L.ptr(offsets), offsets.numel() - 1, L.ptr(out),
+               L.ptr(_f32(g).reshape(1)), L.ptr(d), L.stream())
+        return d, None

@@ -263,6 +263,31 @@ def rot_angle(mat):
     return torch.acos(cos.clamp(-1 + eps, 1 - eps))
 
 
+def matrix_to_quaternion(R):
+    """Rotation matrices R (..., 3, 3) -> unit quaternions (..., 4), real part first and non-negative, in one launch of
+    moda_matrix_to_quat.  The reference calls pytorch3d.transforms.matrix_to_quaternion (train_utils.py:664-666); pytorch3d is
+    absent from the reference tree and unpinned, so this is a restatement, pinned only by the round trip through
+    quaternion_to_matrix.  The rule: with d = (1 + r00 + r11 + r22, 1 + r00 - r11 - r22, 1 - r00 + r11 - r22, 1 - r00 - r11 + r22)
+    = 4 q_k^2, the largest d_k (the best-conditioned branch; a tie goes to the lowest k) selects the candidate 4 q_k q built from d_k
+    and the sums / differences of the off-diagonal entries; it is normalised, and negated when its real part is negative.  R may
+    be a strided view whose last dimension is contiguous, e.g. rtk[:, :3, :3].  No backward: inputs that require grad are refused."""
+    if not torch.is_tensor(R):
+        raise TypeError(f"R: expected a tensor, got {type(R).__name__}")
+    if not R.is_cuda:
+        raise RuntimeError("R must be a CUDA (ROCm) tensor; the HIP library is the only compute path")
+    if R.dtype != torch.float32 or R.dim() < 2 or tuple(R.shape[-2:]) != (3, 3):
+        raise ValueError(f"R: expected an fp32 tensor of shape (..., 3, 3), got {R.dtype} {tuple(R.shape)}")
+    if R.requires_grad:
+        raise NotImplementedError("R: matrix_to_quaternion has no backward kernel; pass R.detach()")
+    lead = R.shape[:-2]
+    if R.dim() != 3 or R.stride(2) != 1 or R.stride(1) < 3 or R.stride(0) < 0:
+        R = R.reshape(-1, 3, 3).contiguous()
+    q = torch.empty((R.shape[0], 4), device=R.device)
+    if R.shape[0]:
+        L.call("moda_matrix_to_quat", L.ptr(R), R.shape[0], R.stride(0), R.stride(1), L.ptr(q), L.stream())
+    return q.view(lead + (4,))
+
+
 def K2mat(K):
     """geom_utils.py:596-612: K (...,4) = fx, fy, px, py -> (bs,3,3)."""
     K = K.view(-1, 4)

@@ -416,7 +416,7 @@ def loss_filter(g_floerr, flo_loss_samp, sil_at_samp_flo, scale_factor=10):
 _OFFSETS = {}
 
 
-def _offset_table(data_offset, T, device):
+def _offset_table(data_offset, T, device, what="compute_root_sm_2nd_loss"):
     """The videos' frame ranges as a device int32 table, uploaded once per distinct tuple."""
     off = tuple(int(v) for v in (data_offset.tolist() if hasattr(data_offset, "tolist") else data_offset))
     if len(off) < 2 or off[0] < 0 or off[-1] > T or any(b < a for a, b in zip(off, off[1:])):
@@ -425,7 +425,7 @@ def _offset_table(data_offset, T, device):
     t = _OFFSETS.get(key)
     if t is None:
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("compute_root_sm_2nd_loss: a new data_offset is uploaded from the host -- call once before capture")
+            raise RuntimeError(f"{what}: a new data_offset is uploaded from the host -- call once before capture")
         t = torch.tensor(off, dtype=torch.int32).to(device)
         _OFFSETS[key] = t
     return t
@@ -444,6 +444,94 @@ def compute_root_sm_2nd_loss(rtk_all, data_offset):
     consecutive frame triples of every video [data_offset[v], data_offset[v + 1]); NaN when no video has three frames.  One
     kernel forward, one backward (a gather per frame: no atomics, the same bits on every run)."""
     return root_sm_parts(rtk_all, data_offset)[0]
+
+
+# ---- the warm-up stages that run before the first forward_default call (moda_amd/warmup.py) ----------------------------------------
+def _warm_tensor(t, what, shape_txt, ok_shape):
+    """A warm-up input as its kernel reads it: a contiguous fp32 device tensor.  Nothing is converted: CPU tensors raise
+    RuntimeError, another dtype / shape / layout ValueError, each naming the argument."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what}: expected a tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} must be a CUDA (ROCm) tensor; the HIP library is the only compute path")
+    if t.dtype != torch.float32 or not ok_shape(t.shape) or not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous fp32 tensor of shape {shape_txt}, got {t.dtype} {tuple(t.shape)}, "
+                         f"contiguous={t.is_contiguous()}")
+    return t
+
+
+def _pose_rows(t, what):
+    return _warm_tensor(t, what, "(T, 4, 4) or (T, 3, 4)", lambda s: len(s) == 3 and s[0] >= 1 and s[1] in (3, 4) and s[2] == 4)
+
+
+def shape_targets(u, obj_bound, bound_factor, use_ellips=True):
+    """The sample points and SDF targets of shape_init_loss (loss_utils.py:546-563) in one launch of moda_shape_target:
+    u (n,3) uniforms in [0, 1), obj_bound (3,) -> (pts (1,n,3) = (u * 2) * bound - bound with bound = obj_bound * bound_factor,
+    bit-equal to the reference on the same u; dis (n,), the signed distance to the ellipsoid with the semi-axes obj_bound scaled by
+    their mean, or to the sphere of radius min(obj_bound))."""
+    u = _warm_tensor(u, "u", "(n, 3)", lambda s: len(s) == 2 and s[0] >= 1 and s[1] == 3)
+    if u.requires_grad:
+        raise NotImplementedError("u: uniforms that require grad are not implemented (the samples have no backward kernel)")
+    ob = _warm_tensor(obj_bound, "obj_bound", "(3,)", lambda s: tuple(s) == (3,)).detach()
+    n = u.shape[0]
+    pts = torch.empty((1, n, 3), device=u.device)
+    dis = torch.empty((n,), device=u.device)
+    L.call("moda_shape_target", L.ptr(u), n, L.ptr(ob), float(bound_factor), int(bool(use_ellips)), L.ptr(pts), L.ptr(dis), L.stream())
+    return pts, dis
+
+
+def shape_init_loss(pts, faces, mlp, embed, bound_factor, use_ellips=True, *, nsample=10000, u=None, obj_bound=None, dy_sum=None):
+    """loss_utils.py:540-572: pull the coarse SDF towards the ellipsoid (use_ellips) or sphere of the template's bound.  pts (V,3)
+    the template vertices (a device tensor); `faces` is accepted and unused -- the reference builds a trimesh from it and never
+    reads it.  u (n,3): the uniforms of this step, a device tensor used as given (what pins a call to a reference run, and what a
+    captured step refills); None draws torch.rand((nsample, 3)) on the device.  obj_bound (3,): the cached pts.abs().amax(0); None
+    computes it on the device.  The network runs as mlp.train_forward(..., sigma_only=True) when gradients are wanted, else as
+    mlp.fused(..., sigma_only=True); the loss is autograd.ShapeLossFn.  dy_sum (1,): a device buffer that the backward fills with
+    the sum of the loss' gradient over the network's outputs, in a fixed order: the gradient of mlp.sigma.bias with the same bits on
+    every run (the network's own backward adds that sum with float atomics; WarmupHarness writes this one over it).  Nothing is
+    read back: with u given the call can be captured.  -> the loss, a 0-dim tensor."""
+    pts = _warm_tensor(pts, "pts", "(V, 3)", lambda s: len(s) == 2 and s[0] >= 1 and s[1] == 3)
+    if obj_bound is None:
+        obj_bound = pts.detach().abs().amax(0)                                         # :548
+    if u is None:
+        if int(nsample) < 1:
+            raise ValueError(f"nsample must be positive, got {nsample}")
+        u = torch.rand((int(nsample), 3), device=pts.device)                           # :550 (the reference draws on the CPU)
+    pts_samp, dis = shape_targets(u, obj_bound, bound_factor, use_ellips)
+    if torch.is_grad_enabled() and any(p.requires_grad for p in mlp.parameters()):
+        y = mlp.train_forward(pts_samp, embed, sigma_only=True)
+    else:
+        y = mlp.fused(pts_samp, n_freq=embed.N_freqs, alpha=embed.alpha, sigma_only=True)
+    return A.ShapeLossFn.apply(y.reshape(-1), dis, dy_sum)
+
+
+def rtk_loss(rtk, rtk_raw, aux_out):
+    """loss_utils.py:151-163: 0.01 * mean rot_angle(Rp Rg^T) + mean |tp - tg|^2 over the predicted poses rtk (T, 3 | 4, 4) and
+    the table rtk_raw (T, 3 | 4, 4); aux_out['rot_loss'] and aux_out['trn_loss'] are filled with 0-dim device tensors, each
+    differentiable on its own.  One launch forward, one backward (a thread per frame); no gradient flows to rtk_raw."""
+    r, gt = _pose_rows(rtk, "rtk"), _pose_rows(rtk_raw, "rtk_raw")
+    if gt.shape[0] != r.shape[0]:
+        raise ValueError(f"rtk_raw: {gt.shape[0]} frames, rtk has {r.shape[0]}")
+    total, rot, trn = A.RtkLossFn.apply(r, gt.detach())
+    aux_out['rot_loss'] = rot
+    aux_out['trn_loss'] = trn
+    return total
+
+
+def root_sm1_parts(rtk_all, data_offset):
+    """-> (loss, parts (3,) detached = [1e-3 * mean angle, 0.1 * mean trn, #pairs]) of compute_root_sm_loss."""
+    r = _pose_rows(rtk_all, "rtk_all")
+    return A.RootSm1Fn.apply(r, _offset_table(data_offset, r.shape[0], r.device, "compute_root_sm_loss"))
+
+
+def compute_root_sm_loss(rtk_all, data_offset):
+    """loss_utils.py:520-537: 1e-3 * mean rot_angle(R_i R_{i+1}^T) + 0.1 * mean |t_i - t_{i+1}| over the consecutive frame pairs
+    of every video [data_offset[v], data_offset[v + 1]), the pairs of all videos pooled before the means.  The degenerate cases
+    follow the rule of compute_root_sm_2nd_loss here: a video too short for a pair (length 0 or 1) contributes none, as the
+    reference's empty slices do, and when no video has a pair the loss is NaN, the mean of an empty set (gradient zero).  The
+    translation norm's gradient at a zero difference is 0, torch's sub-gradient.  One kernel forward, one backward (a gather per
+    frame: no atomics, the same bits on every run)."""
+    return root_sm1_parts(rtk_all, data_offset)[0]
 
 
 # flags of moda.py the assembly reads, with the reference's defaults (moda.py:53-172)
