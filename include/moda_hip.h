@@ -1271,6 +1271,50 @@ int moda_root_sm1_bwd(const float* rtk, int32_t rows, int64_t T, const int32_t* 
  * which is divided by its norm and negated when its first entry is negative.  MODA_ESHAPE: T < 1, T >= 2^31. */
 int moda_matrix_to_quat(const float* R, int64_t T, int64_t mat_stride, int64_t row_stride, float* quat, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Novel-view frame rendering: the two ends around render_rays of scripts/visualize/nvs.py -- construct_rays_nvs (:41-55) for the
+ * pixels inside a silhouette, and the thresholding and canvas assembly of :160-174
+ * (moda_amd/csrc/nvs_kernels.hip; purely additive entries of ABI 11: no existing signature changed, so
+ * moda_abi_version() stays 11).  Nothing allocates, synchronises or reads back, every launch goes to `stream`.  No float
+ * atomics, integer prefix sums in a fixed structure: the same bits on every run.  B frames of S x S pixels, B S S < 2^31.
+ * ------------------------------------------------------------------------ */
+#define MODA_NVS_SCAN_TILE 1024      /* pixels of a frame that one workgroup counts and scans */
+#define MODA_NVS_MAX_TILES 16777216  /* B ceil(S S / MODA_NVS_SCAN_TILE) stays below this */
+
+/* moda_mask_compact_tiles: B ceil(S S / MODA_NVS_SCAN_TILE), the tiles of a call; -1 where moda_mask_compact answers MODA_ESHAPE
+ * (a size < 1, B S S >= 2^31, MODA_NVS_MAX_TILES tiles or more). */
+int64_t moda_mask_compact_tiles(int64_t B, int64_t S);
+
+/* moda_mask_compact: masks (B,S,S) fp32 (is_u8 == 0) or uint8, a pixel kept where its value is > 0 (NaN, -0.0 and negatives are
+ * not) -> offsets (B + 1) int32, frame b's kept pixels are the list entries [offsets[b], offsets[b + 1]); pix and frame
+ * (B S S entries of room each, offsets[B] written) int32, y S + x and b of every kept pixel in frame-major, row-major order;
+ * rank (B,S,S) int32, the pixel's list position or -1.  tile_ws: 2 x tiles int32, caller's.  Three launches: per-wave ballots
+ * and popcounts summed to tile sums, one workgroup over the tile sums, the tile scans.  MODA_EINVAL: a NULL pointer. */
+int moda_mask_compact(const void* masks, int32_t is_u8, int64_t B, int64_t S, int32_t* tile_ws, int32_t* offsets, int32_t* pix,
+                      int32_t* frame, int32_t* rank, void* stream);
+
+/* moda_nvs_rays: the rays of the n listed pixels, one thread each.  Per frame: Rmat (B,3,3), Tmat (B,3), Kinv (B,3,3),
+ * near_far (B,2).  Per ray i with f = frame[i], (x, y) = (pix[i] % S, pix[i] / S): xys (n,2) = (x, y); rays_d (n,3), rays_o (n,3)
+ * with the bits moda_raycast gives the same pixel; near (n), far (n) = near_far[f].  A second launch, one thread per output
+ * float, copies per-frame rows to per-ray rows: rtk_vec (n,21) = [Rmat | Tmat | Kinv][f] (NULL: skipped), and for each of env,
+ * time, bone with a non-NULL *_out: *_out (n, *_c) = *_rows (B, *_c)[f].  An entry of frame outside [0, B) or of pix outside
+ * [0, S S) is not read through: that ray's outputs are NaN.  n == 0 launches nothing.
+ * MODA_ESHAPE: n < 0, n >= 2^31, B S S >= 2^31, a width outside 0..65536, n times the widest row >= 2^32.  MODA_EINVAL: NULL. */
+int moda_nvs_rays(const int32_t* pix, const int32_t* frame, int64_t n, int64_t S, int64_t B, const float* Rmat, const float* Tmat,
+                  const float* Kinv, const float* near_far, float* xys, float* rays_d, float* rays_o, float* near, float* far,
+                  float* rtk_vec, const float* env_rows, int64_t env_c, float* env_out, const float* time_rows, int64_t time_c,
+                  float* time_out, const float* bone_rows, int64_t bone_c, float* bone_out, void* stream);
+
+/* moda_nvs_assemble: the canvases of nvs.py:160-174, one thread per canvas pixel, which reads rank (B,S,S) and gathers: no fill
+ * launch, no scatter.  Per-ray inputs rgb_in (n,3), depth_in, sil_in, vis_in (n).  Outputs fp32: rgb (B,S,S,3), depth, sil, vis
+ * (B,S,S).  rank < 0 (or >= n): 1 in all four.  Otherwise with s = sil_in[r]: s < 0.5 -> sil 0 and rgb 1, else sil s and rgb
+ * copied (a NaN s is not below 0.5); depth and vis copied.  rgb8 (B,S,S,3), sil8, vis8 (B,S,S) uint8, all three or none:
+ * clip(rint(v * 255), 0, 255) of the fp32 outputs, the product rounded to fp32, round half to even, NaN -> 0.
+ * MODA_ESHAPE: a size < 1, B S S >= 2^31, n outside [0, B S S].  MODA_EINVAL: NULL, or only some of the uint8 outputs. */
+int moda_nvs_assemble(const int32_t* rank, int64_t B, int64_t S, int64_t n, const float* rgb_in, const float* depth_in,
+                      const float* sil_in, const float* vis_in, float* rgb, float* depth, float* sil, float* vis, uint8_t* rgb8,
+                      uint8_t* sil8, uint8_t* vis8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,11 @@ _SIGNATURES = {
     "moda_root_sm1_fwd": (_c.c_int, [_P, _I32, _I64, _P, _I32, _P, _P]),
     "moda_root_sm1_bwd": (_c.c_int, [_P, _I32, _I64, _P, _I32, _P, _P, _P, _P]),
     "moda_matrix_to_quat": (_c.c_int, [_P, _I64, _I64, _I64, _P, _P]),
+    # novel-view frames: mask -> ray list, rays of the list, canvas assembly (nvs_kernels.hip): additive, the ABI stays 11
+    "moda_mask_compact_tiles": (_I64, [_I64, _I64]),
+    "moda_mask_compact": (_c.c_int, [_P, _I32, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "moda_nvs_rays": (_c.c_int, [_P, _P, _I64, _I64, _I64] + [_P] * 10 + [_P, _I64, _P] * 3 + [_P]),
+    "moda_nvs_assemble": (_c.c_int, [_P, _I64, _I64, _I64] + [_P] * 12),
 }
 
 EXPORTS = tuple(_SIGNATURES)

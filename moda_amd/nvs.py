@@ -1,0 +1,265 @@
+"""Novel-view frame rendering, device-resident: what scripts/visualize/nvs.py does per frame between the loaded trajectory and
+the written pictures (and render_vid / nerf_render in evaluation mode) -- construct_rays_nvs (:41-55) for the pixels inside a
+reference silhouette, the chunked render_rays loop (:120-159), the thresholding and the `ones` canvases (:160-174), the crop to
+the short edge (:176-185) -- for ALL frames of a trajectory in one batch.  The two ends are four HIP entries
+(csrc/nvs_kernels.hip): moda_mask_compact turns the masks into one ray list, moda_nvs_rays builds the list's rays and per-ray
+code rows, moda_nvs_assemble gathers the per-ray results into images.  The middle is render_rays as it stands.
+
+The host reads back ONE thing: the (B + 1) frame offsets of the ray list, once for the whole batch (the list's length decides
+every later allocation and grid).  The per-ray results never leave the device.
+
+Deviations from the reference, all deliberate:
+  * The ray list of a batch is flat: 'bs' is 1 and 'nsample' the total ray count, frame-major, row-major inside a frame (the
+    order of xys[:, rndmask]); the reference renders one frame per call.  A single (S, S) mask given with several cameras is
+    applied to every frame, as the reference's indexing would, but comes out in the same flat layout.
+  * Masks arrive at render size: the reference's cv2.resize of the silhouettes is not restated, a shape mismatch raises.
+  * The 8-bit outputs restate what cv2.imwrite does to a float image -- clip(rint(v * 255), 0, 255), round half to even,
+    NaN -> 0 -- from OpenCV's source; the restatement has not been run against OpenCV.  rgb8 is RGB (the reference reverses
+    the channels for cv2 at the call).
+  * lbs and the flow warps are refused with NotImplementedError, as everywhere in this package.
+Out of scope: reading trajectories and silhouettes (load_root, load_sils) and writing videos."""
+import collections
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .feeders import chunk_rays, update_delta_rts
+from .geom_utils import K2inv
+
+SCAN_TILE = 1024          # moda_hip.h MODA_NVS_SCAN_TILE
+MAX_PIXELS = 2 ** 31      # B S S stays below this
+
+NVSFrames = collections.namedtuple("NVSFrames", "rgb depth sil vis rgb8 sil8 vis8 offsets", defaults=(None, None, None, None))
+NVSFrames.__doc__ = """rgb (B,S,S,3), depth, sil, vis (B,S,S) fp32 device tensors; rgb8, sil8, vis8 the uint8 images (None unless
+to_uint8); offsets: the (B + 1) frame offsets of the ray list, a host int64 tensor."""
+
+RayList = collections.namedtuple("RayList", "offsets pix frame rank counts")
+
+
+def _no_grad(what, *tensors):
+    if any(torch.is_tensor(t) and t.requires_grad for t in tensors):
+        raise NotImplementedError(f"{what}: inputs that require grad are not implemented (novel-view rendering is evaluation "
+                                  "and has no backward); pass them detached")
+
+
+def _check_masks(what, masks):
+    if not torch.is_tensor(masks):
+        raise TypeError(f"{what}: masks must be a tensor, got {type(masks)}")
+    if masks.dim() != 3 or masks.shape[1] != masks.shape[2] or min(masks.shape) < 1:
+        raise ValueError(f"{what}: masks must be (B, S, S) with B, S >= 1, got {tuple(masks.shape)}")
+    B, S = int(masks.shape[0]), int(masks.shape[1])
+    if B * S * S >= MAX_PIXELS:
+        raise ValueError(f"{what}: masks of {tuple(masks.shape)} hold {B * S * S} pixels, the limit is 2^31 - 1 a call")
+    if masks.dtype not in (torch.float32, torch.uint8) or not masks.is_contiguous():
+        raise ValueError(f"{what}: masks must be contiguous torch.float32 or torch.uint8, got {masks.dtype}, "
+                         f"contiguous={masks.is_contiguous()}")
+    _no_grad(what, masks)
+    return B, S
+
+
+def _compact(what, masks):
+    B, S = _check_masks(what, masks)
+    if not masks.is_cuda:
+        raise RuntimeError(f"{what} takes CUDA (ROCm) tensors; the HIP library is the only compute path")
+    tiles = int(L.load().moda_mask_compact_tiles(B, S))
+    if tiles < 0:
+        raise ValueError(f"{what}: masks of {tuple(masks.shape)} make too many scan tiles of {SCAN_TILE} pixels")
+    dev = masks.device
+    i32 = lambda *s: torch.empty(s, device=dev, dtype=torch.int32)
+    ws, offsets, pix, frame, rank = i32(2 * tiles), i32(B + 1), i32(B * S * S), i32(B * S * S), i32(B, S, S)
+    L.call("moda_mask_compact", L.ptr(masks), 1 if masks.dtype == torch.uint8 else 0, B, S, L.ptr(ws), L.ptr(offsets), L.ptr(pix),
+           L.ptr(frame), L.ptr(rank), L.stream())
+    host = offsets.cpu().long()                      # the one read-back of a batch
+    n = int(host[-1])
+    return RayList(offsets, pix[:n], frame[:n], rank, host)
+
+
+def mask_to_pixels(masks):
+    """masks (B, S, S), fp32 or uint8, a pixel kept where its value is > 0 (as torch.Tensor(mask) > 0 decides: NaN, -0.0 and
+    negatives are not) -> (offsets (B + 1), pix (n), frame (n), rank (B, S, S)), int32 device tensors: pix = y * S + x and frame
+    of every kept pixel, frame-major and row-major inside a frame; frame b's pixels are pix[offsets[b]:offsets[b + 1]]; rank is
+    the pixel's position in the list, or -1.  The same bits on every run.  One synchronisation (the list's length)."""
+    r = _compact("mask_to_pixels", masks)
+    return r.offsets, r.pix, r.frame, r.rank
+
+
+def _cameras(what, rtks, device, scale=None):
+    rtks = torch.as_tensor(np.asarray(rtks, np.float32) if not torch.is_tensor(rtks) else rtks)
+    _no_grad(what, rtks)
+    rtks = rtks.to(device=device, dtype=torch.float32)
+    if rtks.dim() != 3 or tuple(rtks.shape[1:]) != (4, 4):
+        raise ValueError(f"{what}: rtks must be (bs, 4, 4) = [R | T ; fx fy px py], got {tuple(rtks.shape)}")
+    if scale is not None:
+        rtks = rtks.clone()
+        rtks[:, 3] = rtks[:, 3] * scale                                              # nvs.py:85
+    Rmat = rtks[:, :3, :3].contiguous()
+    Tmat = rtks[:, :3, 3].contiguous()
+    Kinv = K2inv(rtks[:, 3]).contiguous()
+    return rtks, Rmat, Tmat, Kinv
+
+
+def _as_masks(what, rndmask, img_size, bs, device):
+    """The reference's torch.Tensor(rndmask).view(-1) > 0 for one frame, or a batch of masks: -> (bs, S, S) on the device."""
+    S = int(img_size)
+    m = rndmask if torch.is_tensor(rndmask) else torch.from_numpy(np.ascontiguousarray(rndmask))
+    if m.dtype == torch.bool:
+        m = m.to(torch.uint8)
+    elif m.dtype not in (torch.float32, torch.uint8):
+        m = m.to(torch.float32)                                                      # torch.Tensor(rndmask)
+    if m.numel() == S * S and bs > 1:
+        m = m.reshape(1, S, S).expand(bs, S, S)
+    if m.numel() != bs * S * S:
+        raise ValueError(f"{what}: the mask holds {m.numel()} pixels, {bs} frame(s) of {S} x {S} hold {bs * S * S} "
+                         "(masks arrive at render size: they are not resized here)")
+    return m.reshape(bs, S, S).contiguous().to(device)
+
+
+def _rays(what, lst, S, Rmat, Tmat, Kinv, near_far, rows=None):
+    """The rays dict of the listed pixels (flat layout), plus the gathered per-frame rows of `rows` {key: (B, C)}."""
+    B = Rmat.shape[0]
+    dev = Rmat.device
+    if near_far is None:                                                             # raycast's own default, geom_utils.py:772-776
+        z = Tmat[:, 2:3]
+        near_far = torch.cat([(z - 1.5).clamp_min(1e-5), z + 1.5], 1)
+    _no_grad(what, near_far)
+    nf = L.dev(near_far if torch.is_tensor(near_far) else torch.as_tensor(np.asarray(near_far, np.float32)).to(dev)).reshape(-1, 2)
+    if nf.shape[0] != B:
+        raise ValueError(f"{what}: near_far holds {nf.shape[0]} rows for {B} frames")
+    n = lst.pix.shape[0]
+    f32 = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)
+    out = {'rays_o': f32(1, n, 3), 'rays_d': f32(1, n, 3), 'near': f32(1, n, 1), 'far': f32(1, n, 1), 'rtk_vec': f32(1, n, 21),
+           'xys': f32(1, n, 2)}
+    rows = rows or {}
+    slots = []
+    for key in ('env_code', 'time_embedded', 'bone_rts'):
+        t = rows.get(key)
+        if t is None:
+            slots += [None, 0, None]
+            continue
+        t = L.dev(t.detach()).reshape(B, -1)
+        out[key] = f32(1, n, t.shape[1])
+        slots += [L.ptr(t), t.shape[1], L.ptr(out[key])]
+        rows[key] = t                                                                # kept alive until the launch is queued
+    L.call("moda_nvs_rays", L.ptr(lst.pix), L.ptr(lst.frame), n, S, B, L.ptr(Rmat), L.ptr(Tmat), L.ptr(Kinv), L.ptr(nf), L.ptr(out['xys']),
+           L.ptr(out['rays_d']), L.ptr(out['rays_o']), L.ptr(out['near']), L.ptr(out['far']), L.ptr(out['rtk_vec']), *slots, L.stream())
+    out['nsample'] = n
+    out['bs'] = 1
+    return out
+
+
+def construct_rays_nvs(img_size, rtks, near_far, rndmask, device):
+    """nvs.py:41-55 with the reference's signature: the rays of the pixels of `rndmask` that are > 0, as the dict raycast
+    returns (rays_o, rays_d (1, n, 3), near, far (1, n, 1), rtk_vec (1, n, 21), xys (1, n, 2), nsample = n, bs = 1).
+    rtks (bs, 4, 4) numpy or tensor; rndmask one (S, S) mask (numpy or tensor, any layout with S * S elements), or (bs, S, S),
+    one mask per camera, which the reference cannot take.  rays_d and rays_o carry the bits of moda_amd.raycast on the same
+    pixels.  One synchronisation (the ray count)."""
+    rtks, Rmat, Tmat, Kinv = _cameras("construct_rays_nvs", rtks, device)
+    masks = _as_masks("construct_rays_nvs", rndmask, img_size, rtks.shape[0], device)
+    lst = _compact("construct_rays_nvs", masks)
+    return _rays("construct_rays_nvs", lst, int(img_size), Rmat, Tmat, Kinv, near_far)
+
+
+def _assemble(rank, n, counts, rgb, depth, sil, vis, to_uint8):
+    B, S = rank.shape[0], rank.shape[1]
+    dev = rank.device
+    if rgb.numel() != 3 * n or any(t.numel() != n for t in (depth, sil, vis)):
+        raise ValueError(f"nvs: per-ray results of {[tuple(t.shape) for t in (rgb, depth, sil, vis)]} for {n} rays")
+    ins = [L.dev(t.detach()).reshape(n, c) for t, c in ((rgb, 3), (depth, 1), (sil, 1), (vis, 1))]
+    f32 = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)
+    u8 = lambda *s: torch.empty(s, device=dev, dtype=torch.uint8) if to_uint8 else None
+    o = [f32(B, S, S, 3), f32(B, S, S), f32(B, S, S), f32(B, S, S), u8(B, S, S, 3), u8(B, S, S), u8(B, S, S)]
+    L.call("moda_nvs_assemble", L.ptr(rank), B, S, n, *(L.ptr(t) if n else None for t in ins), *(L.ptr(t) for t in o), L.stream())
+    return NVSFrames(*o, offsets=counts)
+
+
+def assemble_frames(rank, rgb, depth, sil, vis, to_uint8=False):
+    """nvs.py:160-174 for a batch: rank (B, S, S) int32 from mask_to_pixels, per-ray results rgb (n, 3), depth, sil, vis (n) or
+    (n, 1) in list order -> NVSFrames.  Outside the mask every canvas is 1; inside, sil < 0.5 gives sil 0 and rgb 1, depth and
+    vis are copied.  to_uint8 adds the 8-bit images (see the module docstring).  No synchronisation (offsets is None)."""
+    if not torch.is_tensor(rank) or rank.dtype != torch.int32 or rank.dim() != 3 or rank.shape[1] != rank.shape[2] \
+            or not rank.is_contiguous():
+        raise ValueError("assemble_frames: rank must be the contiguous (B, S, S) int32 tensor of mask_to_pixels")
+    _no_grad("assemble_frames", rgb, depth, sil, vis)
+    if not rank.is_cuda:
+        raise RuntimeError("assemble_frames takes CUDA (ROCm) tensors; the HIP library is the only compute path")
+    return _assemble(rank, rgb.reshape(-1, 3).shape[0], None, rgb, depth, sil, vis, to_uint8)
+
+
+def render_nvs(model, rtks, masks, embedid, near_far=None, ndepth=None, chunk=None, scale=None, to_uint8=False):
+    """The per-frame loop of nvs.py:92-192 for a whole trajectory: rtks (B, 4, 4) cameras (numpy or tensor; `scale` multiplies
+    the intrinsics row, nvs.py:85), masks (B, S, S) fp32 | uint8 device tensor at render size, embedid (B,) frame ids ->
+    NVSFrames(rgb (B,S,S,3), depth, sil, vis (B,S,S)[, rgb8, sil8, vis8], offsets).
+
+    near_far None: get_near_far over the vertices of model.latest_vars['mesh_rest'] with every frame marked seen (nvs.py:92-98).
+    Env code, pose code and bones come from model.env_code, model.pose_code, model.nerf_body_rts (evaluated once per frame, made
+    relative to the rest pose by update_delta_rts, then copied to the frame's rays).  ndepth and chunk default to
+    model.opts.ndepth / .chunk.  The chunk loop runs over the concatenated rays of all frames, so a chunk may straddle frames;
+    render_rays is called with perturb=0, noise_std=0, use_fine=True, render_vis=True.  Nothing is read back except the frame
+    offsets of the ray list."""
+    from .rendering import render_rays
+    opts = model.opts
+    if getattr(opts, 'lbs', False) or 'flowbw' in model.nerf_models or 'flowfw' in model.nerf_models:
+        raise NotImplementedError("render_nvs: linear blend skinning and the flow warps are not implemented (MoDA runs neudbs)")
+    B, S = _check_masks("render_nvs", masks)
+    if not masks.is_cuda:
+        raise RuntimeError("render_nvs takes CUDA (ROCm) tensors; the HIP library is the only compute path")
+    dev = masks.device
+    rtks, Rmat, Tmat, Kinv = _cameras("render_nvs", rtks, dev, scale)
+    embedid = torch.as_tensor(embedid).to(dev).long().reshape(-1)
+    if rtks.shape[0] != B or embedid.shape[0] != B:
+        raise ValueError(f"render_nvs: {rtks.shape[0]} cameras and {embedid.shape[0]} frame ids for {B} masks")
+    ndepth = int(opts.ndepth if ndepth is None else ndepth)
+    chunk = int(opts.chunk if chunk is None else chunk)
+    if chunk < 1:
+        raise ValueError(f"render_nvs: chunk = {chunk}")
+    with torch.no_grad():
+        if near_far is None:                                                         # nvs.py:92-98
+            from .frame_state import FrameState, get_near_far
+            state = FrameState(B, dev)
+            state.rtk.copy_(rtks)
+            state.idk.fill_(1.0)
+            near_far = get_near_far(state.near_far, state, pts=model.latest_vars['mesh_rest'].vertices)
+        lst = _compact("render_nvs", masks)
+        frame_rays = {'time_embedded': model.pose_code(embedid)[:, None]}            # nvs.py:123-132, one row per frame
+        if getattr(model, 'env_code', None) is not None:
+            frame_rays['env_code'] = model.env_code(embedid)[:, None]
+        if 'bones' in model.nerf_models and getattr(opts, 'neudbs', True):
+            frame_rays['bone_rts'] = model.nerf_body_rts(embedid)
+            update_delta_rts(model, frame_rays)
+        rays = _rays("render_nvs", lst, S, Rmat, Tmat, Kinv, near_far, rows=frame_rays)
+        n = rays['nsample']
+        results = collections.defaultdict(list)
+        obj_bound = model.latest_vars['obj_bound']
+        for j in range(0, n, chunk):                                                 # nvs.py:138-154
+            out = render_rays(model.nerf_models, model.embeddings, chunk_rays(rays, j, chunk), N_samples=ndepth, perturb=0,
+                              noise_std=0, chunk=chunk, use_fine=True, img_size=S, obj_bound=obj_bound, render_vis=True, opts=opts)
+            for k in ('img_coarse', 'depth_rnd', 'sil_coarse', 'vis_pred'):
+                results[k].append(out[k].reshape(out[k].shape[0], 3 if k == 'img_coarse' else 1))
+        if n:
+            rgb, depth, sil, vis = (torch.cat(results[k], 0) for k in ('img_coarse', 'depth_rnd', 'sil_coarse', 'vis_pred'))
+        else:
+            rgb, depth, sil, vis = (torch.empty((0, c), device=dev) for c in (3, 1, 1, 1))
+        return _assemble(lst.rank, n, lst.counts, rgb, depth, sil, vis, to_uint8)
+
+
+def _crop(t, h, w, rgb):
+    S = t.shape[-2]
+    if t.dim() < (3 if rgb else 2) or (t.shape[-3] if rgb else t.shape[-1]) != S:
+        raise ValueError(f"crop_short_edge: expected (..., S, S) or (..., S, S, 3), got {tuple(t.shape)}")
+    if h > w:                                                                        # 'vert': the columns [:short]
+        short = int(w * S / h)
+        return t[..., :, :short, :] if rgb else t[..., :, :short]
+    short = int(h * S / w)                                                           # 'hori': the rows [:short]
+    return t[..., :short, :, :] if rgb else t[..., :short, :]
+
+
+def crop_short_edge(frames, h, w):
+    """nvs.py:176-185: the canvases are squares of the long edge of an (h, w) source; a portrait source (h > w) keeps the columns
+    [:short], any other the rows [:short], short = int(short edge * S / long edge).  frames: an NVSFrames -> an NVSFrames of
+    views; or one tensor, (..., S, S), or (..., S, S, 3) with S != 3 -> a view."""
+    if isinstance(frames, NVSFrames):
+        return frames._replace(**{k: _crop(getattr(frames, k), h, w, k.startswith("rgb")) for k in NVSFrames._fields[:7]
+                                  if getattr(frames, k) is not None})
+    t = frames
+    return _crop(t, h, w, t.dim() >= 3 and t.shape[-1] == 3 and t.shape[-3] == t.shape[-2] != 3)
