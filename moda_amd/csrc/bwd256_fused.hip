@@ -39,9 +39,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-#ifndef B256_PIN
-#define B256_PIN 1
-#endif
 constexpr int MT = 64;                 // samples per tile
 constexpr int HI = 128;                // input columns per workgroup
 constexpr int XROW = HI * 2, XS = MT * XROW;
@@ -138,11 +135,7 @@ __global__ __launch_bounds__(512, 1) void bwd256_kernel(B256Args a) {
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)lds;
     const unsigned wave_u = (unsigned)__builtin_amdgcn_readfirstlane(wave);
     auto issue = [&](int k) __attribute__((always_inline)) {     // tile k of this stream -> stage k % 3 (any k: past the end it is zeros)
-#ifdef B256_ABL_NODMA
-        const unsigned m0 = 0xffffff00u;     // every row out of range: the instruction stream stays, nothing is fetched
-#else
         const unsigned m0 = ((unsigned)p + (unsigned)k * (unsigned)P) * MT;
-#endif
         const unsigned st = lds0 + (unsigned)(k % NSTAGE) * STAGE;
 #pragma unroll
         for (int i = 0; i < ZPW; ++i) dma16(dz_rs, st + ((unsigned)ZPW * wave_u + i) * 1024u, zdma[i] + m0 * ldz2);
@@ -181,11 +174,7 @@ __global__ __launch_bounds__(512, 1) void bwd256_kernel(B256Args a) {
             for (int u = 0; u < KW; ++u) {
                 union { unsigned short s[8]; bf16x8 v; } t;
 #pragma unroll
-#ifdef B256_ABL_NOWREG
-                for (int e = 0; e < 8; ++e) t.s[e] = (unsigned short)(0x3c00 + lane + u + e + ldw);
-#else
                 for (int e = 0; e < 8; ++e) t.s[e] = wp[(16 * u + 8 * h + e) * ldw];
-#endif
                 wreg[u] = t.v;
             }
         }
@@ -217,15 +206,9 @@ __global__ __launch_bounds__(512, 1) void bwd256_kernel(B256Args a) {
                 for (int mb = 0; mb < 2; ++mb) zb[u][mb] = *(const bf16x8*)(St + zkf + 32 * mb * ZROW + 16 * ((2 * u + h) ^ fz));
 #pragma unroll
             for (int u = 0; u < KW; ++u) {
-#if B256_PIN
                 __builtin_amdgcn_sched_barrier(0);      // keep the read-ahead: hipcc otherwise sinks every read to its MFMA (lgkmcnt(0) per MFMA)
-#endif
-#ifndef B256_ABL_NODX
 #pragma unroll
                 for (int mb = 0; mb < 2; ++mb) accx[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wreg[u], zb[u % AH][mb], accx[mb], 0, 0, 0);
-#else
-                accx[0][u] += (float)zb[u % AH][0][0] + (float)zb[u % AH][1][1];
-#endif
                 if (u + AH < KW)
 #pragma unroll
                     for (int mb = 0; mb < 2; ++mb) zb[u % AH][mb] = *(const bf16x8*)(St + zkf + 32 * mb * ZROW + 16 * ((2 * (u + AH) + h) ^ fz));
@@ -243,11 +226,7 @@ __global__ __launch_bounds__(512, 1) void bwd256_kernel(B256Args a) {
             for (int e = 0; e < 4; ++e) {
                 const int row = frow + 16 * e;
                 const u32x4_ v = *(const u32x4_*)(Ow + row * 64 + 16 * (fch ^ ((row >> 2) & 3)));
-#ifdef B256_ABL_NOSTORE
-                __builtin_amdgcn_raw_buffer_store_b128(v, ro, 0xffffff00u, 0, 0);
-#else
                 __builtin_amdgcn_raw_buffer_store_b128(v, ro, ovo + (m0 + 16u * e) * ldo2, 0, 0);
-#endif
             }
             // tile k+1 is needed: the DMA of the NSTAGE - 2 tiles behind it and this tile's 4 stores may stay in flight
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((NSTAGE - 2) * DPT + 4) : "memory");
@@ -319,21 +298,13 @@ __global__ __launch_bounds__(512, 1) void bwd256_kernel(B256Args a) {
             frags(0, 0);
 #pragma unroll
             for (int g_ = 0; g_ < NGRP; ++g_) {
-#if B256_PIN
                 __builtin_amdgcn_sched_barrier(0);
-#endif
                 if (g_ + 1 < NGRP) frags(g_ + 1, (g_ + 1) & 1);
-#if B256_PIN
                 __builtin_amdgcn_sched_barrier(0);
-#endif
                 const int u = g_ / NH, hh = g_ % NH;
 #pragma unroll
                 for (int ob = 0; ob < 4; ++ob)
-#ifndef B256_ABL_NODW
                     accw[4 * hh + ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(za[g_ & 1][ob], xb[u & 1], accw[4 * hh + ob], 0, 0, 0);
-#else
-                    accw[4 * hh + ob][u] += (float)za[g_ & 1][ob][0] + (float)xb[u & 1][1];
-#endif
             }
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((NSTAGE - 2) * DPT) : "memory");
         }
@@ -344,11 +315,7 @@ __global__ __launch_bounds__(512, 1) void bwd256_kernel(B256Args a) {
         for (int ob = 0; ob < NOB; ++ob) {
             float* gp = a.gW + (long long)(32 * ob + 4 * h) * a.ldg + half * HI + 32 * ib + l31;
 #pragma unroll
-#ifdef B256_ABL_NOATOM
-            for (int r = 0; r < 16; ++r) if (accw[ob][r] == 1.2345f) gp[r] = 0.f;
-#else
             for (int r = 0; r < 16; ++r) atomicAdd(gp + (long long)((r & 3) + 8 * (r >> 2)) * a.ldg, accw[ob][r]);
-#endif
         }
     }
     if (do_db) {        // the dX waves' threads of a chunk column hold partial sums of the same eight o

@@ -34,11 +34,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KT = 32;                    // k per tile: two 32x32x16 steps
-#ifndef MODA_X3_PF
-#define MODA_X3_PF 1
-#endif
-constexpr int PF = MODA_X3_PF;            // k-tiles of global loads in flight per engine (1 or 2)
-static_assert(PF == 1 || PF == 2, "one or two register stages");
+constexpr int PF = 1;                     // k-tiles of global loads in flight per engine
 constexpr int KF_STRIDE = KT * 2 + 16;    // bytes per row of a k-fast image (80: sixteen consecutive rows cover all 64 banks)
 enum { EPI_ATOMIC = 0, EPI_T = 1 };
 
@@ -94,7 +90,7 @@ DEVINL void split8(float4 a, float4 b, uint4 (&o)[NS]) {
 // bf16x6 forward 326 vs 302 us, masked dX 401 vs 306 us on random operands): the workgroup-wide barrier ties each group to the
 // slower phase of the other.  PMC of these forms: MFMA busy 38 %, VALU 28 %, waves stalled in s_waitcnt 46 % of their cycles (8 % of them on LDS).)
 template <int NS, int TR, int TC, bool XKF, bool YKF, int EPI, int NG = 1>
-__global__ __launch_bounds__(256 * NG, NG == 1 ? (NS == 2 && PF == 1 ? 3 : 2) : 1) void gemm_x3_kernel(X3Args a) {
+__global__ __launch_bounds__(256 * NG, NG == 1 ? (NS == 2 ? 3 : 2) : 1) void gemm_x3_kernel(X3Args a) {
     static_assert(NS == 2 || NS == 3, "two or three bf16 images per operand");
     static_assert(NG == 1 || EPI == EPI_ATOMIC, "wave groups split k: the dW form");
     static_assert(!XKF || EPI == EPI_T, "a k-fast X is the weight of the forward form");
@@ -314,27 +310,17 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? (NS == 2 && PF == 1 ? 3 : 2) : 
         }
     };
     // k-tile t of this engine is staged (registers -> split -> LDS images) one barrier before it is multiplied; the loads of tile
-    // t + PF are issued right after that barrier.  PF = 2 (a load has two tiles' time to land) measured the same as PF = 1 within
+    // t + PF are issued right after that barrier.  PF = 2 (a second register stage: a load has two tiles' time to land) measured the same as PF = 1 within
     // the box-to-box spread (256-wide forms 3-10 % faster, 64-wide 5-10 % slower, the training step +-2 %): these kernels are not
     // waiting for memory latency but adding up their phases (split VALU + LDS writes | barrier | LDS reads + MFMA | barrier)
     // with only two workgroups per CU to overlap them.  PF = 1 keeps 40-50 registers fewer.
     if (nit > 0) fetch(std::integral_constant<int, 0>{}, kbeg);
-    if (PF > 1 && nit > 1) fetch(std::integral_constant<int, PF - 1>{}, kbeg + kstep);
     for (int it = 0; it < nit; it += PF) {      // (a k-tile past the end loads zeros)
-        {
-            stash(std::integral_constant<int, 0>{}, kbeg + it * kstep);
-            __syncthreads();
-            if (it + PF < nit) fetch(std::integral_constant<int, 0>{}, kbeg + (it + PF) * kstep);
-            multiply();
-            __syncthreads();
-        }
-        if (PF > 1 && it + 1 < nit) {
-            stash(std::integral_constant<int, PF - 1>{}, kbeg + (it + 1) * kstep);
-            __syncthreads();
-            if (it + 1 + PF < nit) fetch(std::integral_constant<int, PF - 1>{}, kbeg + (it + 1 + PF) * kstep);
-            multiply();
-            __syncthreads();
-        }
+        stash(std::integral_constant<int, 0>{}, kbeg + it * kstep);
+        __syncthreads();
+        if (it + PF < nit) fetch(std::integral_constant<int, 0>{}, kbeg + (it + PF) * kstep);
+        multiply();
+        __syncthreads();
     }
 
     // C/D map: lane l register r -> T row (r&3) + 8(r>>2) + 4(l>>5), T column l & 31

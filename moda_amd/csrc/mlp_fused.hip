@@ -35,86 +35,23 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef MODA_BF16_WAVES
-#define MODA_BF16_WAVES 8          // waves per workgroup of the bf16 instantiations (4: one per SIMD, 8: two)
-#endif
-#ifndef MODA_BF16_CB128
-#define MODA_BF16_CB128 2          // ... of the 128-wide bf16 / fp16 inference kernels on long uniform batches (dispatch); 1 = off
-#endif
-#ifndef MODA_BF16_CB
-#define MODA_BF16_CB 1             // 32-sample column blocks per wave of the bf16 instantiations
-#endif
-#ifndef MODA_BF16_CB64
-#define MODA_BF16_CB64 1           // column blocks per wave of the 64-wide bf16 instantiation
-#endif
-#ifndef MODA_BF16_WAVES64
-#define MODA_BF16_WAVES64 16       // waves per workgroup of the 64-wide bf16 instantiation (resident weights, <= 128 VGPRs)
-#endif
-#ifndef MODA_RING
-#define MODA_RING 6
-#endif
-#ifndef MODA_STAGGER
-#define MODA_STAGGER 0             // 8-wave kernels: SIMD partners run one ring chunk apart (measured: no gain)
-#endif
-#ifndef MODA_RESIDENT
-#define MODA_RESIDENT 1            // 64-wide bf16 nets keep their whole weight stream in LDS
-#endif
-#ifndef MODA_APIPE
-#define MODA_APIPE 2               // A fragments read ahead of their MFMA
-#endif
-#ifndef MODA_HEAD_PREFETCH
-#define MODA_HEAD_PREFETCH 0       // 1: UNI kernels load a tile's positions and row-bias rows one tile ahead.  It won 8 % on the
-#endif                             // 5 x 64 kernel in round 1; now its 15 registers cost more (spills) than the wait: off is
-                                   // 3.7 % faster on the 8 x 256 kernel and 2.5 % on the skin + warp kernel (A/B, r02)
-#ifndef MODA_DMA_LEADERS
-#define MODA_DMA_LEADERS 0         // 1: one wave per SIMD issues all LDS-DMA pieces of the weight stream (measured: 12 % slower)
-#endif
-#ifndef MODA_DMA_SPLIT
-#define MODA_DMA_SPLIT 0           // 1: a wave issues its LDS-DMA pieces of one chunk half a chunk apart (measured: no gain)
-#endif
-#ifndef MODA_XLAYER
-#define MODA_XLAYER 0              // 1: hidden layers hand their last output tile's epilogue to the next layer's first tile.
-#endif                             // Measured: +1.6 % slower alone (the accumulator set kept across the layer boundary spills),
-                                   // +2 % slower than off with the head prefetch off as well -- a negative result, kept as an option
-#ifndef MODA_X3_EPI_PIPE
-#define MODA_X3_EPI_PIPE 0         // split-bf16 kernels: software-pipelined tile epilogue (needs the second accumulator set)
-#endif
-#ifndef MODA_X3_WAVES256
-#define MODA_X3_WAVES256 4         // waves per workgroup of the 256-wide split-bf16 kernel (2 x 128 activation registers)
-#endif
-#ifndef MODA_X3_WAVES128
-#define MODA_X3_WAVES128 4         // ... of the 128-wide one (8 waves' PE stash + ring do not fit the 160 KB of LDS)
-#endif
-#ifndef MODA_X3_WAVES
-#define MODA_X3_WAVES 8            // ... of the 64-wide one
-#endif
-#ifndef MODA_RING_SAFE
-#define MODA_RING_SAFE 1           // refill the slot of the chunk before last (see Ring::kInFlight); 0: the racy schedule of rounds 1-3
-#endif
-#ifndef MODA_F16_TRACK
-#define MODA_F16_TRACK 1           // fp16 kernels: keep the running maximum of the packed activations for the overflow report (0: timing A/B)
-#endif
-#ifndef MODA_AGPR_APIPE
-#define MODA_AGPR_APIPE 4          // the AGPR kernel's fragment read-ahead (it has the registers for more than MODA_APIPE; a power of
-                                   // two: with 3 or 6 the unrolled layer loses its constant register numbers).  2 -> 4: -1.0 % (A/B, one box)
-#endif
-#ifndef MODA_AGPR_PREFETCH
-#define MODA_AGPR_PREFETCH 0       // the AGPR kernel loads a tile's positions and row-bias rows one tile ahead (MODA_HEAD_PREFETCH)
-#endif
-#ifndef MODA_AGPR_PREQ
-#define MODA_AGPR_PREQ 0           // 1: read the next layer's first fragments ahead of the current layer's last epilogue.  Measured +1 % SLOWER (the chunk wait then blocks in front of the epilogue instead of behind it; layer 1 doubles): off
-#endif
-#ifndef MODA_AGPR_XLAYER
-#define MODA_AGPR_XLAYER 0         // the AGPR kernel: hidden layers hand their last tile's epilogue to the next layer's first tile (see MODA_XLAYER)
-#endif
-#ifndef MODA_MLP_AGPR_DEFAULT
-#define MODA_MLP_AGPR_DEFAULT 1    // 1: the 8 x 256 bf16 inference kernel takes the AGPR form by default (MODA_MLP_AGPR overrides)
-#endif
-#ifndef MODA_EPI_PIPE
-#define MODA_EPI_PIPE 1            // the epilogue of an output tile is issued between the MFMAs of the next one
-#endif
-constexpr int kAPipe = MODA_APIPE;
-constexpr int kFragBytes = 1024;   // one fragment: 64 lanes x 16 B
+// Tuning parameters (values, not variants: every one of them is what the shipped kernels are built with).
+constexpr int kBf16Waves = 8;       // waves per workgroup of the bf16 instantiations (4: one per SIMD, 8: two)
+constexpr int kBf16Cb128 = 2;       // ... of the 128-wide bf16 / fp16 inference kernels on long uniform batches (dispatch); 1 = off
+constexpr int kBf16Cb = 1;          // 32-sample column blocks per wave of the bf16 instantiations
+constexpr int kBf16Cb64 = 1;        // column blocks per wave of the 64-wide bf16 instantiation
+constexpr int kBf16Waves64 = 16;    // waves per workgroup of the 64-wide bf16 instantiation (resident weights, <= 128 VGPRs)
+constexpr int kRingDepth = 6;       // chunks of the weight ring (see Ring::kInFlight)
+constexpr int kAPipe = 2;           // A fragments read ahead of their MFMA
+constexpr int kAgprAPipe = 4;       // the AGPR kernel's fragment read-ahead (it has the registers for more than kAPipe; a power of
+                                    // two: with 3 or 6 the unrolled layer loses its constant register numbers).  2 -> 4: -1.0 % (A/B, one box)
+constexpr int kX3Waves256 = 4;      // waves per workgroup of the 256-wide split-bf16 kernel (2 x 128 activation registers)
+constexpr int kX3Waves128 = 4;      // ... of the 128-wide one (8 waves' PE stash + ring do not fit the 160 KB of LDS)
+constexpr int kX3Waves = 8;         // ... of the 64-wide one
+constexpr int kDmaSpreadFirst = 9;  // fragments 9, 11, 13, 15 of a chunk: 0.978 -> 0.966 of the eight-wave form's time against 0, 4, 8, 12 (A/B, one box)
+constexpr int kDmaSpreadStep = 2;
+constexpr int kMlpAgprDefault = 1;  // 1: the 8 x 256 bf16 inference kernel takes the AGPR form by default (MODA_MLP_AGPR overrides)
+constexpr int kFragBytes = 1024;    // one fragment: 64 lanes x 16 B
 
 // Diagnostic build (-DMODA_STAMPS): wave 0 of every workgroup adds the s_memtime deltas of its phases into
 // 16 slots of `stamps` (a buffer nothing else reads); never compiled into the shipped library.
@@ -194,35 +131,7 @@ struct MlpArgs {
 // awaited chunk needs a run-time count; done with a compare chain the 8 x 256 kernel spilled (6x slower), done by polling
 // the wave's own counter in IB_STS (s_getreg_b32: vm_cnt[3:0] bits 3:0, vm_cnt[5:4] bits 23:22 -- the decode is right,
 // 20 after 20 loads) it was 3-5x slower.  Measured negative results; the dump kernels keep the strict wait.)
-#ifndef MODA_DMA_SPREAD
-#define MODA_DMA_SPREAD 1          // one-wave-per-SIMD kernels: a chunk's LDS-DMA pieces are issued one at a time, evenly over the chunk
-#endif
-#ifndef MODA_AGPR_REGSTAGE
-#define MODA_AGPR_REGSTAGE 0       // 1: the AGPR kernel stages its weight chunks L2 -> registers -> LDS (buffer_load + ds_write_b128) instead of
-                                   // LDS-DMA.  Measured (round 5, profiles/r05/coarse_kernel_cb2_agpr_ab.md): bit-identical and SLOWER, 12.63-12.74 ms
-                                   // against 12.23 ms -- the LDS-DMA pieces are not what the one-wave-per-SIMD kernel loses its cycles to.
-                                   // (building it needs -mllvm -pragma-unroll-threshold=131072: the staging code pushes the fully unrolled
-                                   // layer past hipcc's default limit and the literal-AGPR operands stop being constants)
-#endif
-#ifndef MODA_STAGE_LOAD0
-#define MODA_STAGE_LOAD0 1         // fragment (of the chunk being fetched) in front of which the first piece of the NEXT chunk is loaded
-#endif
-#ifndef MODA_STAGE_LOADSTEP
-#define MODA_STAGE_LOADSTEP 2
-#endif
-#ifndef MODA_STAGE_STORE0
-#define MODA_STAGE_STORE0 12       // ... and written to LDS
-#endif
-#ifndef MODA_STAGE_STORESTEP
-#define MODA_STAGE_STORESTEP 1
-#endif
-#ifndef MODA_DMA_SPREAD_FIRST
-#define MODA_DMA_SPREAD_FIRST 9    // fragments 9, 11, 13, 15 of a chunk: 0.978 -> 0.966 of the eight-wave form's time against 0, 4, 8, 12 (A/B, one box)
-#endif
-#ifndef MODA_DMA_SPREAD_STEP
-#define MODA_DMA_SPREAD_STEP 2
-#endif
-template <int CHF, int NWAVES, bool RESIDENT, int kRing = MODA_RING, bool SPREAD = false>
+template <int CHF, int NWAVES, bool RESIDENT, int kRing = kRingDepth, bool SPREAD = false>
 struct Ring {
     __amdgpu_buffer_rsrc_t rsrc;   // packed stream (global), as a buffer resource
     uint8_t* lds;          // ring base (LDS)
@@ -231,70 +140,41 @@ struct Ring {
     int issue_slot;        // ring slot the next LDS-DMA chunk goes to
     int pos;               // stream position of the next chunk to issue, modulo nchunks
     int fcount;            // fragments already consumed from the current chunk
-    int late_slot, late_pos;   // chunk whose second half of LDS-DMA pieces is still to be issued (kSplit)
+    int late_slot, late_pos;   // chunk some of whose LDS-DMA pieces are still to be issued (kSpread)
     int lane, wave;
-    bool leader;           // waves [0, NWAVES/2) run one chunk ahead of their SIMD partners [NWAVES/2, NWAVES)
-    f32x4 st[4];           // kStage: this wave's pieces of the NEXT chunk on their way L2 -> registers -> LDS
-    int nxt_slot, nxt_pos; // kStage: where that chunk goes / comes from
+    // Unused.  These members belonged to the deleted SIMD-partner stagger and register-staged copy; without
+    // them hipcc allocates the registers of 14 kernels of this file differently, so they stay until a change that re-measures.
+    bool leader;
+    f32x4 st[4];
+    int nxt_slot, nxt_pos;
 
     static constexpr int kChunkBytes = CHF * kFragBytes;
     // LDS-DMA instructions per wave per chunk; a resident stream may be loaded by the first CHF of more than CHF waves
-    // MODA_DMA_LEADERS: only the first half of the waves (one per SIMD) issue the LDS-DMA pieces of a streamed chunk, twice
-    // as many each; their SIMD partners go straight to their MFMAs.  An LDS-DMA piece costs its wave 60-185 issue cycles
-    // (4 waves x 2 column blocks pay the same 13 % for the stream as 8 x 1: it is issue time, not bytes); with both
-    // partners issuing at the same point of the chunk the matrix pipe of their SIMD idles meanwhile.
-    static constexpr int kWantLoaders = (!RESIDENT && MODA_DMA_LEADERS != 0 && NWAVES >= 8) ? NWAVES / 2 : NWAVES;
-    static constexpr int kLoaders = (CHF >= kWantLoaders) ? kWantLoaders : CHF;
+    static constexpr int kLoaders = (CHF >= NWAVES) ? NWAVES : CHF;
     static constexpr int kPerWave = CHF / kLoaders;
-    static constexpr bool kStagger = (NWAVES == 8) && (MODA_STAGGER != 0);
-    static constexpr bool kSplit = !RESIDENT && !kStagger && (kPerWave >= 2) && (MODA_DMA_SPLIT != 0) && !SPREAD;
     // SPREAD (the four-wave AGPR kernel): with one wave per SIMD nobody issues MFMAs while this wave issues an LDS-DMA piece (60-185
     // cycles each by the guide's table, against 24 cycles of shadow behind an MFMA), and a chunk's four pieces back to back behind
     // the barrier idle the matrix pipe for a fifth of the chunk.  Piece i goes out in front of fragment i * CHF / kPerWave instead.
-    static constexpr bool kSpread = SPREAD && !RESIDENT && !kStagger && (kPerWave >= 2) && (MODA_DMA_SPREAD != 0);
+    static constexpr bool kSpread = SPREAD && !RESIDENT && (kPerWave >= 2);
     // ... and where: in the hidden layers a chunk IS one output tile (16 fragments), whose MFMAs 1..8 carry the previous tile's
-    // epilogue pieces; the LDS-DMA pieces go behind the later, filler-free MFMAs (MODA_DMA_SPREAD_FIRST + i * MODA_DMA_SPREAD_STEP)
-    static constexpr int kSpreadStep = (CHF == 16 && kPerWave == 4) ? MODA_DMA_SPREAD_STEP : CHF / kPerWave;
-    static constexpr int kSpreadFirst = (CHF == 16 && kPerWave == 4) ? MODA_DMA_SPREAD_FIRST : 0;
+    // epilogue pieces; the LDS-DMA pieces go behind the later, filler-free MFMAs (kDmaSpreadFirst + i * kDmaSpreadStep)
+    static constexpr int kSpreadStep = (CHF == 16 && kPerWave == 4) ? kDmaSpreadStep : CHF / kPerWave;
+    static constexpr int kSpreadFirst = (CHF == 16 && kPerWave == 4) ? kDmaSpreadFirst : 0;
     static_assert(!kSpread || (kSpreadFirst + (kPerWave - 1) * kSpreadStep < CHF), "pieces inside the chunk");
-    // chunks that may still be in flight when the chunk a leader needs must have landed
+    // chunks that may still be in flight when the chunk a wave needs must have landed
     // The slot refilled at step s (after its barrier) must be one no wave can still be READING.  A wave issues its fragment
     // reads kAPipe ahead of the MFMAs, so when it arrives at the barrier of step s the ds_reads of chunk s-1's last fragments may
     // still sit in the LDS queue; refilling chunk s-1's slot right after that barrier (kInFlight = kRing - 2, rounds 1-3) races
     // the LDS-DMA against those reads.  The DMA's memory round trip usually wins the race for the reads by a wide margin -- but
     // not always when the LDS pipe is congested: the 128-wide training-forward kernel (4 waves, activation dumps transposed
     // through LDS) computed 32 ... 128 rows of a launch with a stale 1 KiB weight fragment in ~1 % of its launches (round 3's
-    // "unexplained" gradient outliers; found by the soak tests of round 4, tools/dump_fwd_repro.py).  With MODA_RING_SAFE the slot
-    // refilled is chunk s-2's, whose reads every wave has CONSUMED (a whole chunk of MFMAs ago): kRing - 3 chunks in flight,
-    // which measured the same speed as kRing - 2 (a 5-deep ring was within 0.2 % of the 6-deep one).
-    // (With the stagger the followers read chunk s-1 at step s, so the slot that is safe to refill lies one chunk further back
-    //  still: kRing - 4 chunks in flight when both switches are on -- ADVICE r04; MODA_STAGGER is off by default.)
-    // kStage (MODA_AGPR_REGSTAGE, off: an experiment of round 5 kept for its negative result): no LDS-DMA at all.  The idea: an
-    // LDS-DMA piece costs the issuing wave ~60 cycles (guide: 60-185) of which an MFMA's shadow hides 24, and with one wave per
-    // SIMD the rest is matrix-pipe idle time, four times per chunk.  So the four pieces of the NEXT chunk travel as plain 16-byte
-    // buffer loads issued early in the current chunk and are written to the ring with ds_write_b128 late in it, each in a gap of
-    // its own; the chunk barrier stays (with an lgkmcnt wait for the writes instead of a vmcnt wait for the DMA).  Two slots of
-    // the ring are in use at a time (read / being written).  Result: same bits, 3-4 % slower than the DMA ring.
-    static constexpr bool kStage = SPREAD && !RESIDENT && !kStagger && (kPerWave == 4) && (CHF == 16) && (MODA_AGPR_REGSTAGE != 0);
-    static constexpr int kInFlight = (kStagger && MODA_RING_SAFE) ? kRing - 4 : ((kStagger || MODA_RING_SAFE) ? kRing - 3 : kRing - 2);
+    // "unexplained" gradient outliers; found by the soak tests of round 4, tools/dump_fwd_repro.py).  So the slot refilled is
+    // chunk s-2's, whose reads every wave has CONSUMED (a whole chunk of MFMAs ago): kRing - 3 chunks in flight, which measured
+    // the same speed as kRing - 2 (a 5-deep ring was within 0.2 % of the 6-deep one).
+    static constexpr int kInFlight = kRing - 3;
     static_assert(kInFlight >= 1, "the ring is too shallow for this refill schedule");
     static_assert(CHF % kLoaders == 0, "chunk fragments must divide over the loader waves");
 
-    DEVINL void stage_load(int i) {
-        typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-        const u32x4_ v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16, nxt_pos * kChunkBytes + (i * kLoaders + wave) * kFragBytes, 0);
-        st[i] = __builtin_bit_cast(f32x4, v);
-    }
-    DEVINL void stage_store(int i) {
-        *(f32x4*)(lds + nxt_slot * kChunkBytes + (i * kLoaders + wave) * kFragBytes + lane * 16) = st[i];
-    }
-    DEVINL void stage_at(int f) {       // the staging work that belongs in front of fragment f of the chunk being fetched
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (f == MODA_STAGE_LOAD0 + i * MODA_STAGE_LOADSTEP) stage_load(i);
-            if (f == MODA_STAGE_STORE0 + i * MODA_STAGE_STORESTEP) stage_store(i);
-        }
-    }
     DEVINL void issue(int to_slot, int stream_pos, int i0 = 0, int i1 = kPerWave) {
         // buffer form: descriptor + scalar chunk/fragment offset in SGPRs, the per-lane 16 B offset in one VGPR that
         // never changes -- no vector address arithmetic per issue
@@ -308,28 +188,12 @@ struct Ring {
                                                          16, lane * 16, soff + i * kLoaders * kFragBytes, 0, 0);
     }
     // One step of the workgroup-wide schedule: wait for the oldest outstanding chunk, rendezvous, refill the slot
-    // that no wave reads any more.  With the stagger, at step s the leaders read chunk s and their SIMD partners
-    // chunk s-1, so a wave in its VALU epilogue (end of a layer) sits beside a partner that is still issuing
-    // MFMAs; the slot of chunk s-2 is the one refilled (with chunk s + kRing - 2).
+    // that no wave reads any more (chunk s-2's, with chunk s + kInFlight).
     DEVINL void acquire() {
         if (RESIDENT) return;
-        if (kStage) {       // every wave's pieces of this chunk are written (lgkmcnt) before anyone reads it
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            nxt_slot = (slot + 1 == kRing) ? 0 : slot + 1;
-            nxt_pos = pos;
-            pos = (pos + 1 == nchunks) ? 0 : pos + 1;
-            return;
-        }
-#ifdef MODA_ABL_NOBAR
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kInFlight * kPerWave) : "memory");
-#else
         asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(kInFlight * kPerWave) : "memory");
-#endif
-#ifndef MODA_ABL_NODMA
-        // MODA_DMA_SPLIT: only the first LDS-DMA piece goes out here; the rest follows half a chunk later (next()), so
-        // that two pieces do not queue behind each other at the address unit while the wave should be issuing MFMAs
-        issue(issue_slot, pos, 0, kSpread ? (kSpreadFirst == 0 ? 1 : 0) : (kSplit ? kPerWave / 2 : kPerWave));
-#endif
+        // kSpread: only the pieces that belong in front of fragment 0 go out here, the rest one at a time in next()
+        issue(issue_slot, pos, 0, kSpread ? (kSpreadFirst == 0 ? 1 : 0) : kPerWave);
         late_slot = issue_slot;
         late_pos = pos;
         issue_slot = (issue_slot + 1 == kRing) ? 0 : issue_slot + 1;
@@ -343,19 +207,6 @@ struct Ring {
             fcount = 0;
             return;
         }
-        if (kStage) {       // chunk 0 through the registers into slot 0; chunk 1 follows during chunk 0's fragments
-            nxt_slot = 0;
-            nxt_pos = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) stage_load(i);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) stage_store(i);
-            pos = 1 % nchunks;
-            slot = 0;
-            fcount = 0;
-            issue_slot = late_slot = late_pos = 0;
-            return;
-        }
         constexpr int kPrimed = kInFlight + 1;   // chunks issued before the first step
 #pragma unroll
         for (int c = 0; c < kPrimed; ++c) issue(c, c % nchunks);
@@ -363,31 +214,15 @@ struct Ring {
         issue_slot = kPrimed % kRing;
         slot = 0;
         fcount = 0;
-        if (kStagger && !leader) acquire();   // followers sit out step 0
     }
     DEVINL void finish() {
-        if (RESIDENT || kStage) return;
-        if (kStagger && leader) acquire();    // leaders sit out the last step
+        if (RESIDENT) return;
         // every LDS-DMA this wave issued must land before the workgroup's LDS is released
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     // (fcount is a compile-time fact at every call site of the unrolled layers, so these tests fold away)
     DEVINL void issue_rest() {    // SPREAD: a wave that consumes no fragment of this chunk still owes its remaining pieces
-        if (kStage) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) stage_load(i);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) stage_store(i);
-            return;
-        }
-#ifndef MODA_ABL_NODMA
         if (kSpread) issue(late_slot, late_pos, kSpreadFirst == 0 ? 1 : 0, kPerWave);
-#endif
-    }
-    DEVINL void issue_late() {
-#ifndef MODA_ABL_NODMA
-        issue(late_slot, late_pos, kPerWave / 2, kPerWave);
-#endif
     }
     DEVINL void advance() {
         fcount = 0;
@@ -395,40 +230,19 @@ struct Ring {
     }
     DEVINL f32x4 next() {
         if (fcount == 0) acquire();
-#ifdef MODA_ABL_NOLDS
-        f32x4 v = {1.f, 2.f, 3.f, 4.f};
-        asm volatile("" : "+v"(v));
-#else
         const f32x4 v = *(const f32x4*)(lds + slot * kChunkBytes + fcount * kFragBytes + lane * 16);
-#endif
-        if (kStage) stage_at(fcount);
-        if (kSplit && fcount == CHF / 2) issue_late();     // before fragment CHF/2 is consumed
-        if (!kStage && kSpread && fcount > 0 && fcount >= kSpreadFirst && (fcount - kSpreadFirst) % kSpreadStep == 0 &&
-            (fcount - kSpreadFirst) / kSpreadStep < kPerWave) {
-#ifndef MODA_ABL_NODMA
+        if (kSpread && fcount > 0 && fcount >= kSpreadFirst && (fcount - kSpreadFirst) % kSpreadStep == 0 &&
+            (fcount - kSpreadFirst) / kSpreadStep < kPerWave)
             issue(late_slot, late_pos, (fcount - kSpreadFirst) / kSpreadStep, (fcount - kSpreadFirst) / kSpreadStep + 1);
-#endif
-        }
         if (++fcount == CHF) advance();
         return v;
     }
     DEVINL void end_layer() {   // layers are padded to whole chunks
         if (fcount != 0) {
-            if (kSplit && fcount <= CHF / 2) issue_late();   // ended before the half-way point: the second half is still owed
-            if (kStage) {                                    // the next chunk's loads / writes that this short layer did not reach
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (MODA_STAGE_LOAD0 + i * MODA_STAGE_LOADSTEP >= fcount) stage_load(i);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (MODA_STAGE_STORE0 + i * MODA_STAGE_STORESTEP >= fcount) stage_store(i);
-            }
-            if (!kStage && kSpread) {                        // pieces of this chunk's refill that are still owed
-#ifndef MODA_ABL_NODMA
+            if (kSpread) {      // pieces of this chunk's refill that are still owed
 #pragma unroll
                 for (int i = (kSpreadFirst == 0 ? 1 : 0); i < kPerWave; ++i)
                     if (kSpreadFirst + i * kSpreadStep >= fcount) issue(late_slot, late_pos, i, i + 1);
-#endif
             }
             advance();
         }
@@ -584,12 +398,8 @@ struct PrecBF16 {
         for (int q = 0; q < 30; ++q) {
             const int k = q / 3;
             const int c = q - 3 * k;
-#ifdef MODA_ABL_NOPE   // timing-only ablation build: no sine
-            v[q] = win_lds[k] * __builtin_fmaf(t[c], (float)(1 << k), phase);
-#else
             const float rev = __builtin_amdgcn_fractf(__builtin_fmaf(t[c], (float)(1 << k), phase));
             v[q] = win_lds[k] * __builtin_amdgcn_sinf(rev);
-#endif
         }
         v[30] = h ? y : x;
         v[31] = h ? 0.f : z;
@@ -630,41 +440,23 @@ struct PrecBF16 {
 // (4) an accumulator whose registers the compiler may REUSE right behind the chain's last MFMA statement (the sigma head: only
 // row 0 is read) -- the hardware writes all 16 registers ~32 cycles after issue, into whatever lives there by then: settle()
 // right behind the chain (found as non-repeatable outputs; with the builtin the hazard recogniser pads this WAW itself).
-// debugging knobs (numbers, -DMODA_AGPR_PRE_NOP=7 ...): wait states ahead of an epilogue piece / behind it / ahead of an MFMA
-#define MODA_STR2(x) #x
-#define MODA_STR(x) MODA_STR2(x)
-#ifdef MODA_AGPR_PRE_NOP
-#define MODA_AGPR_PRE "s_nop " MODA_STR(MODA_AGPR_PRE_NOP) "\n\t"
-#else
-#define MODA_AGPR_PRE ""
-#endif
-#ifdef MODA_AGPR_POST_NOP
-#define MODA_AGPR_POST "\n\ts_nop " MODA_STR(MODA_AGPR_POST_NOP)
-#else
-#define MODA_AGPR_POST ""
-#endif
-#ifdef MODA_AGPR_MFMA_NOP
-#define MODA_AGPR_MFMA_PRE "s_nop " MODA_STR(MODA_AGPR_MFMA_NOP) "\n\t"
-#else
-#define MODA_AGPR_MFMA_PRE ""
-#endif
 struct PrecBF16A : PrecBF16 {
     struct Act { int base; };            // first of the tile's eight AGPRs
     static constexpr int kRegX = 0, kRegY = 128, kRegBlock = 64, kRegTile = 8;
     static DEVINL void mma_act(f32x16& acc, const f32x4& a, const Act& x, int sub) {
-        asm volatile(MODA_AGPR_MFMA_PRE "v_mfma_f32_32x32x16_bf16 %0, %1, a[%c2:%c3], %0" : "+v"(acc) : "v"(a), "i"(x.base + 4 * sub), "i"(x.base + 4 * sub + 3));
+        asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, a[%c2:%c3], %0" : "+v"(acc) : "v"(a), "i"(x.base + 4 * sub), "i"(x.base + 4 * sub + 3));
     }
     static DEVINL void mma_pe(f32x16& acc, const f32x4& a, const Pe& p, int g) {
-        asm volatile(MODA_AGPR_MFMA_PRE "v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(p.b[g]));
+        asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(p.b[g]));
     }
     // accumulator registers 2p, 2p+1 -> dword (p & 3) of sub-step p >> 2 (PrecBF16::store_piece), i.e. AGPR base + p
     static DEVINL void store_piece(Act& x, const f32x16& acc, bool relu, int p, unsigned&) {
         float tmp;
         if (relu)
-            asm volatile(MODA_AGPR_PRE "v_cvt_pk_bf16_f32 %0, %1, %2\n\tv_pk_max_i16 %0, %0, 0\n\tv_accvgpr_write_b32 a[%c3], %0" MODA_AGPR_POST
+            asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2\n\tv_pk_max_i16 %0, %0, 0\n\tv_accvgpr_write_b32 a[%c3], %0"
                          : "=&v"(tmp) : "v"(acc[2 * p]), "v"(acc[2 * p + 1]), "i"(x.base + p));
         else
-            asm volatile(MODA_AGPR_PRE "v_cvt_pk_bf16_f32 %0, %1, %2\n\tv_accvgpr_write_b32 a[%c3], %0" MODA_AGPR_POST
+            asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2\n\tv_accvgpr_write_b32 a[%c3], %0"
                          : "=&v"(tmp) : "v"(acc[2 * p]), "v"(acc[2 * p + 1]), "i"(x.base + p));
     }
     static DEVINL void store_act(Act& x, const f32x16& acc, bool relu, unsigned& trk) {
@@ -738,10 +530,8 @@ struct PrecF16 {
     // maximum of |acc[0]| as an integer (inf = 0x7f800000, NaNs above).  Two VALU operations per tile (an earlier version kept
     // the maximum of every packed pair: 8 per tile, +2 % on the 8 x 256 kernel and +6 % on the skin + warp kernel).
     static DEVINL void note(unsigned& trk, float v) {
-#if MODA_F16_TRACK
         const unsigned b = __builtin_bit_cast(unsigned, v) & 0x7fffffffu;
         trk = b > trk ? b : trk;
-#endif
     }
     static DEVINL void store_act(Act& x, const f32x16& acc, bool relu, unsigned& trk) {
         note(trk, acc[0]);
@@ -817,24 +607,22 @@ struct PrecF16A : PrecF16 {
     struct Act { int base; };
     static constexpr int kRegX = 0, kRegY = 128, kRegBlock = 64, kRegTile = 8;
     static DEVINL void mma_act(f32x16& acc, const f32x4& a, const Act& x, int sub) {
-        asm volatile(MODA_AGPR_MFMA_PRE "v_mfma_f32_32x32x16_f16 %0, %1, a[%c2:%c3], %0" : "+v"(acc) : "v"(a), "i"(x.base + 4 * sub), "i"(x.base + 4 * sub + 3));
+        asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, a[%c2:%c3], %0" : "+v"(acc) : "v"(a), "i"(x.base + 4 * sub), "i"(x.base + 4 * sub + 3));
     }
     static DEVINL void mma_pe(f32x16& acc, const f32x4& a, const Pe& p, int g) {
-        asm volatile(MODA_AGPR_MFMA_PRE "v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(p.b[g]));
+        asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(p.b[g]));
     }
     static DEVINL void store_piece(Act& x, const f32x16& acc, bool relu, int p, unsigned& trk) {
         float tmp;
-#if MODA_F16_TRACK
         if (p == 0) {            // the overflow probe (PrecF16::note) on accumulator register 0, inside the statement
             unsigned t2;
             asm volatile("v_and_b32 %1, 0x7fffffff, %2\n\tv_max_u32 %0, %0, %1" : "+v"(trk), "=&v"(t2) : "v"(acc[0]));
         }
-#endif
         if (relu)
-            asm volatile(MODA_AGPR_PRE "v_cvt_pk_f16_f32 %0, %1, %2\n\tv_pk_max_i16 %0, %0, 0\n\tv_accvgpr_write_b32 a[%c3], %0" MODA_AGPR_POST
+            asm volatile("v_cvt_pk_f16_f32 %0, %1, %2\n\tv_pk_max_i16 %0, %0, 0\n\tv_accvgpr_write_b32 a[%c3], %0"
                          : "=&v"(tmp) : "v"(acc[2 * p]), "v"(acc[2 * p + 1]), "i"(x.base + p));
         else
-            asm volatile(MODA_AGPR_PRE "v_cvt_pk_f16_f32 %0, %1, %2\n\tv_accvgpr_write_b32 a[%c3], %0" MODA_AGPR_POST
+            asm volatile("v_cvt_pk_f16_f32 %0, %1, %2\n\tv_accvgpr_write_b32 a[%c3], %0"
                          : "=&v"(tmp) : "v"(acc[2 * p]), "v"(acc[2 * p + 1]), "i"(x.base + p));
     }
     static DEVINL void store_act(Act& x, const f32x16& acc, bool relu, unsigned& trk) {
@@ -991,7 +779,6 @@ struct PrecBF16x3 {
 };
 
 DEVINL float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }
-DEVINL void keep_alive(const f32x16& v) { asm volatile("" ::"v"(v)); }   // timing-only ablation builds
 
 // ---------------------------------------------------------------------------------------------
 // Kernel.  A layer is processed one 32-row OUTPUT tile at a time: initialise one accumulator tile from the bias,
@@ -1015,7 +802,7 @@ DEVINL void keep_alive(const f32x16& v) { asm volatile("" ::"v"(v)); }   // timi
 // HX on the 8 x 256 kernel (HXR): the rgb head alone -- 128 terms per colour with nothing behind them but a sigmoid, 6.6e-5 of
 // the colour scale with single fp16 operands against 2.3e-6 with the head's weights and activations split; dir_encoding's epilogue
 // packs the residuals beside the roundings (actd_lo), the head issues 3 MFMAs per fragment pair: +16 MFMAs on ~1050 per tile.
-template <int W, typename P, int CB, int NWAVES, bool ENDY, bool UNI, bool WARP = false, int DUMP = 0, int RING = MODA_RING,
+template <int W, typename P, int CB, int NWAVES, bool ENDY, bool UNI, bool WARP = false, int DUMP = 0, int RING = kRingDepth,
           bool COMP = false, bool HX = false>
 __global__ __launch_bounds__(NWAVES * 64) __attribute__((amdgpu_waves_per_eu(NWAVES / 4, NWAVES / 4)))
 void mlp_fused_kernel(MlpArgs a) {
@@ -1025,15 +812,15 @@ void mlp_fused_kernel(MlpArgs a) {
     static_assert(!COMP || (UNI && !WARP && DUMP == 0 && CB == 1 && std::is_same<P, PrecBF16>::value),
                   "the compositing epilogue is built for the bf16 UNI inference kernels");
     static_assert(!WARP || (UNI && !std::is_same<P, PrecF32>::value), "the warp epilogue is built for the bf16-geometry UNI kernels");
-    // DUMP: 0 none, 1 fp32 activation dumps, 2 bf16 dumps by lane-pair swap, 3 / 4 bf16 dumps through a per-wave LDS transpose
-    // of two tiles / one tile (a template parameter: with several store forms in one body the 8 x 256 kernel spills)
+    // DUMP: 0 none, 1 fp32 activation dumps, 2 bf16 dumps by lane-pair swap, 3 bf16 dumps through a per-wave LDS transpose
+    // of two tiles (a template parameter: with several store forms in one body the 8 x 256 kernel spills)
     static_assert(!DUMP || (std::is_same<P, PrecBF16>::value && !WARP), "activation dumps are built for the bf16 kernels");
     constexpr int NTHREADS = NWAVES * 64;
     constexpr int NT = W / 32;                        // 32-row tiles of a hidden layer
     constexpr int NTD = (NT / 2 > 0) ? NT / 2 : 1;    // tiles of the dir_encoding layer (W/2 rows)
     constexpr int CHF = (W == 64) ? 8 : 16;           // fragments per ring chunk
     constexpr int TILE = NWAVES * 32 * CB;            // samples per workgroup iteration
-    constexpr bool RESIDENT = (W == 64) && kIs16<P> && (MODA_RESIDENT != 0);
+    constexpr bool RESIDENT = (W == 64) && kIs16<P>;   // the 64-wide bf16 / fp16 nets keep their whole weight stream in LDS
     using RingT = Ring<CHF, NWAVES, RESIDENT, RING, kAsmMfma<P>>;
     const int ring_chunks = RESIDENT ? a.nchunks : RING;
 
@@ -1047,8 +834,8 @@ void mlp_fused_kernel(MlpArgs a) {
     f32x4* pe_lds = (f32x4*)(rb_slots + NWAVES * CB * RBW) + threadIdx.x;
     constexpr int PE_VEC = sizeof(typename P::Pe) / 16;   // 16-byte pieces per lane and column block
     // DUMP == 3: per wave and column block, a 4 KB transpose buffer of the activation dump ([32 samples][64 features] bf16)
-    constexpr int TBW = (DUMP == 4) ? 2048 : 4096;       // bytes per wave and column block
-    constexpr int TBRS = (DUMP == 4) ? 64 : 128;         // bytes per sample row
+    constexpr int TBW = 4096;                            // bytes per wave and column block
+    constexpr int TBRS = 128;                            // bytes per sample row
     unsigned char* const tbuf = (unsigned char*)(rb_slots + NWAVES * CB * RBW) + sizeof(typename P::Pe) * CB * NTHREADS +
                                 (threadIdx.x >> 6) * (CB * TBW);
 
@@ -1067,20 +854,8 @@ void mlp_fused_kernel(MlpArgs a) {
     ring.nchunks = a.nchunks;
     ring.lane = lane;
     ring.wave = wave;
-    ring.leader = wave < NWAVES / 2;
+    ring.leader = wave < NWAVES / 2;     // (unused: see Ring)
     ring.prime();
-    // PREQ (the AGPR kernel): the first fragments of the NEXT layer are read from LDS while the current layer's last tile is
-    // still being converted -- the chunk barrier, the LDS-DMA wait and the LDS latency at every layer boundary pass under the
-    // epilogue instead of in front of the layer's first MFMA (one wave per SIMD: nobody else uses the matrix pipe meanwhile).
-    constexpr int PREQ = (kAsmMfma<P> && MODA_AGPR_PREQ != 0) ? MODA_AGPR_APIPE : 0;
-    typename P::Frag preq[PREQ > 0 ? PREQ : 1];
-    auto prefetch_next = [&]() __attribute__((always_inline)) {
-        if constexpr (PREQ > 0) {
-#pragma unroll
-            for (int d = 0; d < PREQ; ++d) preq[d] = P::fetch(ring);
-        }
-    };
-    prefetch_next();
 
     const bool with_sigma = (a.flags & (MODA_MLP_WITH_SIGMA | MODA_MLP_SIGMA_ONLY)) != 0;
     const bool sigma_only = (a.flags & MODA_MLP_SIGMA_ONLY) != 0;
@@ -1121,7 +896,6 @@ void mlp_fused_kernel(MlpArgs a) {
             // per-set code rows folded only at the first row of a run of identical sets (moda_fold_rows with run_start): read there
             if (a.rows_at_runs) r1u = a.run_start[r1u];
         }
-#ifndef MODA_ABL_NOHEADLOAD
         if (uni) {
             if (lane < W / 4) {
                 hd.rb[0] = *(const f32x4*)(a.rb1 + (long long)r1u * W + 4 * lane);
@@ -1130,32 +904,15 @@ void mlp_fused_kernel(MlpArgs a) {
             if (lane < NTD * 8 && (a.flags & MODA_MLP_SIGMA_ONLY) == 0)
                 hd.rb[2] = *(const f32x4*)(a.rbd + (long long)rdu * (NTD * 32) + 4 * lane);
         }
-#endif
         bool ok;
         const long long mm = sample_at(t, cb, ok);
-#ifdef MODA_ABL_NOHEADLOAD   // timing-only ablation build: no global loads at the head of a tile
-        hd.x = 0.001f * (float)(mm & 1023);
-        hd.y = 0.002f * (float)(lane);
-        hd.z = 0.3f;
-#else
         hd.x = a.xyz[mm * 3 + 0];
         hd.y = a.xyz[mm * 3 + 1];
         hd.z = a.xyz[mm * 3 + 2];
-#endif
         if (a.flip != nullptr && a.flip[mm]) hd.x = -hd.x;
         return hd;
     };
-    // UNI kernels request a tile's head one tile ahead (after the encoding of the current tile has consumed the
-    // registers): the loads then have a whole tile to land in, instead of being waited for at the head of their own tile
-    // (MODA_ABL_NOHEADLOAD: that wait is 8 % of the 5x64 kernel)
-    // (not in the dump kernels: they are short of registers -- the 8 x 256 one spilled 84 dwords per lane, and a scratch
-    //  reload waits on vmcnt like everything else, i.e. for every dump store in flight)
-    constexpr bool PREFETCH = UNI && ((MODA_HEAD_PREFETCH != 0) || (kAsmMfma<P> && MODA_AGPR_PREFETCH != 0)) && (DUMP == 0);
     Head head[CB];
-    if (PREFETCH) {
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) head[cb] = load_head(blockIdx.x, cb, true);
-    }
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         STAMP(15);   // loop overhead / previous tile's tail
         if (UNI && a.n_live != nullptr) {
@@ -1177,10 +934,6 @@ void mlp_fused_kernel(MlpArgs a) {
                     ring.issue_rest();
                     ring.advance();
                 }
-                if (PREFETCH) {
-#pragma unroll
-                    for (int cb = 0; cb < CB; ++cb) head[cb] = load_head(tile + gridDim.x, cb, true);
-                }
                 continue;
             }
         }
@@ -1198,7 +951,7 @@ void mlp_fused_kernel(MlpArgs a) {
                 const int r1u = __builtin_amdgcn_readfirstlane(r1), rdu = __builtin_amdgcn_readfirstlane(rd);
                 rb_uni[cb] = __builtin_amdgcn_ballot_w64(r1 != r1u || rd != rdu) == 0ull;
             }
-            if (!PREFETCH) head[cb] = load_head(tile, cb, rb_uni[cb]);
+            head[cb] = load_head(tile, cb, rb_uni[cb]);
         }
         typename P::Pe pe[CB];
 #pragma unroll
@@ -1213,10 +966,6 @@ void mlp_fused_kernel(MlpArgs a) {
                 }
                 if (lane < NTD * 8) *(f32x4*)(slot + 2 * W + 4 * lane) = head[cb].rb[2];
             }
-        }
-        if (PREFETCH) {   // the next tile's head (indices past the end are clamped to valid memory; nothing is stored for them)
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) head[cb] = load_head(tile + gridDim.x, cb, true);
         }
         // fused compositing: the depths this lane's sample needs are requested now and waited for at the end of the tile (loaded
         // there, their round trip -- and the transcendental chain behind it -- ran with the matrix pipe idle on all waves at once)
@@ -1336,7 +1085,7 @@ void mlp_fused_kernel(MlpArgs a) {
                 union { u32x4_ w; bf16x8 b; } o;
                 o.b = x.b[qd >> 1];
                 const int ch = slot * 4 + qd;
-                const int sw = (DUMP == 4) ? ((col >> 1) & 3) : (col & 7);
+                const int sw = col & 7;
                 *(lds_uint2*)(tbuf + cb * TBW + col * TBRS + 16 * (ch ^ sw) + 8 * h) = u32x2v{o.w[2 * (qd & 1)], o.w[2 * (qd & 1) + 1]};
             }
         };
@@ -1347,7 +1096,7 @@ void mlp_fused_kernel(MlpArgs a) {
                 if (ps >= 2 * ntl) continue;
                 const int row = (ntl == 2 ? (lane >> 3) + 8 * ps : (lane >> 2) + 16 * ps);
                 const int ch = ntl == 2 ? (lane & 7) : (lane & 3);
-                const int sw = (DUMP == 4) ? ((row >> 1) & 3) : (row & 7);
+                const int sw = row & 7;
                 const u32x4v v = *(lds_uint4*)(tbuf + cb * TBW + row * TBRS + 16 * (ch ^ sw));
                 const int mm = m_first + row;
                 const unsigned voff = ((unsigned)mm * (unsigned)dld + 8u * (unsigned)ch) * 2u;    // see dump_pair
@@ -1358,9 +1107,9 @@ void mlp_fused_kernel(MlpArgs a) {
         // tile unconverted in set 1 (defer_out) and the next hidden layer converts it piecewise between the MFMAs of its
         // first output tile (pend_in) -- into the last tile of its own source buffer, which those MFMAs read last.  Without
         // it every layer ends with one tile's epilogue (MFMA result latency + 16 VALU) while the matrix pipe idles on all
-        // waves at once: ~3 % of the 8 x 256 kernel by its phase stamps.
-        constexpr bool XL = (((MODA_XLAYER != 0) && std::is_same<P, PrecBF16>::value) || ((MODA_AGPR_XLAYER != 0) && kAsmMfma<P>)) &&
-                            (DUMP == 0) && (W >= 128) && (NT % 2 == 0);
+        // waves at once: ~3 % of the 8 x 256 kernel by its phase stamps.  Measured +1.6 % slower and OFF for good: the hand-off
+        // stays in the source only because two kernels of this file change their register numbers without it.
+        constexpr bool XL = false;
         f32x16 cacc[2][CB];
         typename P::Act actd_lo[HXR ? CB : 1][HXR ? NTD : 1];     // split heads (8 x 256): residuals of dir_encoding's output
         auto layer = [&](auto& src, auto& dst, auto ntout_c, auto ntin_c, const bool with_pe, const bool with_act,
@@ -1372,17 +1121,15 @@ void mlp_fused_kernel(MlpArgs a) {
             constexpr int PEGc = P::PEG;
             const int fpt = (with_pe ? PEGc : 0) + (with_act ? NTI * P::SUBS : 0);   // fragments per output tile
             const int NF = NTO * fpt;                                                 // fragments of this layer, in stream order
-            constexpr int AP = kAsmMfma<P> ? MODA_AGPR_APIPE : kAPipe;     // fragments read ahead of their MFMA
+            constexpr int AP = kAsmMfma<P> ? kAgprAPipe : kAPipe;          // fragments read ahead of their MFMA
             typename P::Frag q[AP];
 #pragma unroll
-            for (int d = 0; d < AP; ++d) {
-                if constexpr (PREQ > 0) q[d] = preq[d];
-                else if (d < NF) q[d] = P::fetch(ring);
-            }
-            // (bf16 kernels only: the fp32 parity kernels keep 2 x 128 activation registers and have no room for a
-            // second accumulator set -- pipelined, their allocation collapsed into AGPR copies and scratch, 3x slower)
-            if constexpr ((MODA_EPI_PIPE != 0) && (kIs16<P> ||
-                                                   (std::is_same<P, PrecBF16x3>::value && (MODA_X3_EPI_PIPE != 0)))) {
+            for (int d = 0; d < AP; ++d)
+                if (d < NF) q[d] = P::fetch(ring);
+            // (16-bit kernels only: the fp32 parity kernels keep 2 x 128 activation registers and have no room for a
+            // second accumulator set -- pipelined, their allocation collapsed into AGPR copies and scratch, 3x slower;
+            // the split-bf16 kernels would need the second set as well)
+            if constexpr (kIs16<P>) {
             // Software pipeline over the output tiles, two accumulator sets in ping-pong: while tile rt accumulates, the
             // epilogue of tile rt-1 (ReLU + pack into dst, 8 pieces) is issued piecewise between its MFMAs and, once
             // that set is free again, the bias of tile rt+1 is read into it.  Written sequentially (one accumulator,
@@ -1433,8 +1180,8 @@ void mlp_fused_kernel(MlpArgs a) {
                                         if (split_out) P::store_piece_lo(actd_lo[cb][(rt - 1) % NTD], c[oth][cb], p);
                                     }
                                     if (DUMP && dptr != nullptr) {
-                                        if (DUMP >= 3) {
-                                            constexpr int G = (DUMP == 3 && NTO % 2 == 0) ? 2 : 1;      // tiles per flush
+                                        if (DUMP == 3) {
+                                            constexpr int G = (NTO % 2 == 0) ? 2 : 1;      // tiles per flush
                                             if (p & 1) tb_put(cb, (rt - 1) % G, p >> 1, dst[cb][rt - 1]);
                                             if (p == 7 && (rt - 1) % G == G - 1) tb_flush(dptr, dld, cb, rt - G, G);
                                         } else if (DUMP == 2) {
@@ -1485,10 +1232,6 @@ void mlp_fused_kernel(MlpArgs a) {
                         }
                 }
             }
-            if constexpr (PREQ > 0) {                 // every fragment of this layer has been read: on to the next layer's chunk
-                ring.end_layer();
-                prefetch_next();
-            }
             if (!(XL && defer_out)) {
             settle_acc<P>(c[(NTO - 1) & 1][0]);        // (asm MFMAs: the last tile is converted right behind its MFMAs)
 #pragma unroll
@@ -1498,8 +1241,8 @@ void mlp_fused_kernel(MlpArgs a) {
                     if (split_out) P::store_act_lo(actd_lo[cb][(NTO - 1) % NTD], c[(NTO - 1) & 1][cb]);
                 }
                 if (DUMP && dptr != nullptr) {
-                    if (DUMP >= 3) {
-                        constexpr int G = (DUMP == 3 && NTO % 2 == 0) ? 2 : 1;
+                    if (DUMP == 3) {
+                        constexpr int G = (NTO % 2 == 0) ? 2 : 1;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) tb_put(cb, (NTO - 1) % G, q, dst[cb][NTO - 1]);
                         tb_flush(dptr, dld, cb, NTO - G, G);
@@ -1546,7 +1289,7 @@ void mlp_fused_kernel(MlpArgs a) {
                 for (int cb = 0; cb < CB; ++cb) P::store_act(dst[cb][rt], c[cb], relu, trk);
             }
             }
-            if constexpr (PREQ == 0) ring.end_layer();
+            ring.end_layer();
         };
         using IC_NT = std::integral_constant<int, NT>;
         using IC_NTD = std::integral_constant<int, NTD>;
@@ -1594,19 +1337,10 @@ void mlp_fused_kernel(MlpArgs a) {
             for (int t = 0; t < NT; ++t)
 #pragma unroll
                 for (int sb = 0; sb < P::SUBS; ++sb) {
-                    const int k = t * P::SUBS + sb;
-                    typename P::Frag w;
-                    if constexpr (PREQ > 0) w = preq[k % PREQ]; else w = P::fetch(ring);
+                    const typename P::Frag w = P::fetch(ring);
 #pragma unroll
                     for (int cb = 0; cb < CB; ++cb) P::mma_act(accs[cb], w, hid[cb][t], sb);
-                    if constexpr (PREQ > 0) {
-                        if (k + PREQ < NT * P::SUBS) preq[k % PREQ] = P::fetch(ring);
-                    }
                 }
-            if constexpr (PREQ > 0) {
-                ring.end_layer();
-                prefetch_next();
-            }
             // (asm MFMAs: the compiler treats the statement as finished when it is issued.  Behind this chain it (a) copies the
             //  accumulators at the join of this branch -- v_mov reads of registers the hardware has not written yet: stale sigma in
             //  87 % of the samples, different on every launch -- and (b) reuses the 15 registers of each tile whose rows nobody reads
@@ -1615,7 +1349,7 @@ void mlp_fused_kernel(MlpArgs a) {
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) settle_acc<P>(accs[cb]);
         }
-        if constexpr (PREQ == 0) ring.end_layer();
+        ring.end_layer();
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) P::note(trk, accs[cb][0]);     // (fp16: an overflow of the last hidden layer shows here)
         if (sigma_only) {
@@ -1733,14 +1467,9 @@ void mlp_fused_kernel(MlpArgs a) {
                                 P::mma_act(acco[cb][ot], whi, actd[cb][t], sb);
                             }
                         } else {
-                            const int k = ot * (NTD * P::SUBS) + t * P::SUBS + sb;        // fragment of the head (both tiles)
-                            typename P::Frag w;
-                            if constexpr (PREQ > 0) w = preq[k % PREQ]; else w = P::fetch(ring);
+                            const typename P::Frag w = P::fetch(ring);
 #pragma unroll
                             for (int cb = 0; cb < CB; ++cb) P::mma_act(acco[cb][ot], w, actd[cb][t], sb);
-                            if constexpr (PREQ > 0) {
-                                if (k + PREQ < nout_t * (NTD * P::SUBS)) preq[k % PREQ] = P::fetch(ring);
-                            }
                         }
                     }
 #pragma unroll
@@ -1748,7 +1477,6 @@ void mlp_fused_kernel(MlpArgs a) {
             }
         }
         ring.end_layer();
-        prefetch_next();       // (the next tile's first layer: its chunk arrives while this tile's outputs are stored)
         }
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) P::note(trk, acco[cb][0][0]);  // (fp16: ... of the dir layer here)
@@ -1939,11 +1667,7 @@ void mlp_fused_kernel(MlpArgs a) {
                     px = a.pts_tf[(long long)mm * 3 + 0]; py = a.pts_tf[(long long)mm * 3 + 1]; pz = a.pts_tf[(long long)mm * 3 + 2];
                 }
                 float ox, oy, oz;
-#ifdef MODA_WARP_EXACT_DIV
-                dqs_apply(c8, px, py, pz, &ox, &oy, &oz);
-#else
                 dqs_apply_fast(c8, px, py, pz, &ox, &oy, &oz);
-#endif
                 if (ok && h == 0) {
                     if (a.out != nullptr) {            // (null: the caller wants the cycle distance only)
                         float* o = a.out + (long long)mm * 3;
@@ -1959,11 +1683,6 @@ void mlp_fused_kernel(MlpArgs a) {
             continue;
         }
         // ---- store: out[m, row] for the rgb rows, sigma appended (nerf.py:190-197) ---------------------
-#ifdef MODA_ABL_NOSTORE   // timing-only ablation build: results kept alive, nothing written
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) { keep_alive(acco[cb][0]); keep_alive(acco[cb][1]); keep_alive(accs[cb]); }
-        continue;
-#endif
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) {
             bool ok;
@@ -1990,7 +1709,6 @@ void mlp_fused_kernel(MlpArgs a) {
                 // 32 x 32 tile goes through its (now idle) PE-stash slice of LDS so that a lane writes four consecutive
                 // samples of one channel -- 16-byte stores, eight lanes per 128-byte row segment, instead of 16 dword stores
                 const int m_first = tile * TILE + wave * (32 * CB) + cb * 32;
-#ifndef MODA_ABL_NO_TRSTORE
                 if ((a.out_tr_S & 31) == 0 && m_first + 31 < a.M && !with_sigma) {
                     float* tb = (float*)(pe_lds - threadIdx.x) + (long long)cb * PE_VEC * NTHREADS * 4 + wave * 256;
                     float* ob = a.out + (long long)((unsigned)m_first / (unsigned)a.out_tr_S) * a.out_stride * a.out_tr_S
@@ -2017,7 +1735,6 @@ void mlp_fused_kernel(MlpArgs a) {
                     }
                     continue;
                 }
-#endif
             }
             // The 32 row predicates and row offsets below are the same in every tile; left to itself hipcc computes them once
             // before the tile loop and carries them through it -- in spilled SGPR pairs and 64-bit scratch slots (the dump
@@ -2104,18 +1821,18 @@ static int stream_shape(const moda_mlp_desc* d, StreamShape* s) {
     return 0;
 }
 
-template <int W, typename P, int CB, int NWAVES, bool ENDY, bool UNI, bool WARP = false, int DUMP = 0, int RING = MODA_RING,
+template <int W, typename P, int CB, int NWAVES, bool ENDY, bool UNI, bool WARP = false, int DUMP = 0, int RING = kRingDepth,
           bool COMP = false, bool HX = false>
 static int launch_p(const MlpArgs& a, hipStream_t stream) {
     constexpr int CHF = (W == 64) ? 8 : 16;
     constexpr int TILE = NWAVES * 32 * CB;
     const size_t pe_bytes = sizeof(typename P::Pe) * CB * NWAVES * 64;
-    constexpr bool RESIDENT = (W == 64) && kIs16<P> && (MODA_RESIDENT != 0);
+    constexpr bool RESIDENT = (W == 64) && kIs16<P>;
     const size_t ring_chunks = RESIDENT ? (size_t)a.nchunks : (size_t)RING;
     constexpr int NTD = (W / 64 > 0) ? W / 64 : 1;
     const size_t rb_bytes = (size_t)NWAVES * CB * (2 * W + NTD * 32) * sizeof(float);
     const size_t lds = ring_chunks * CHF * kFragBytes + (size_t)(a.nbias + 16) * sizeof(float) + rb_bytes + pe_bytes +
-                       (DUMP == 3 ? (size_t)NWAVES * CB * 4096 : (DUMP == 4 ? (size_t)NWAVES * CB * 2048 : 0));
+                       (DUMP == 3 ? (size_t)NWAVES * CB * 4096 : 0);
     if (lds > 160 * 1024) return MODA_ESHAPE;
     // the attribute is per device: one bit per device ordinal and instantiation (a benign race only repeats the call),
     // so a process that drives several GPUs sets it on each of them
@@ -2137,7 +1854,7 @@ static int launch_p(const MlpArgs& a, hipStream_t stream) {
 }
 
 // the last hidden layer (index D-1 of layers 2..D, alternating X->Y, Y->X) writes Y when D-1 is odd
-template <int W, typename P, int CB, int NWAVES, int DUMP = 0, int RING = MODA_RING, bool HX = false>
+template <int W, typename P, int CB, int NWAVES, int DUMP = 0, int RING = kRingDepth, bool HX = false>
 static int launch(const MlpArgs& a, hipStream_t stream) {
     // column blocks start at multiples of 32 samples; row = min(m / div, R - 1)
     const bool uni = (a.R1 == 1 || a.div1 % 32 == 0) && (a.Rd == 1 || a.divd % 32 == 0);
@@ -2182,9 +1899,9 @@ template <typename P>
 static int wide128(const MlpArgs& a, hipStream_t st) {
     const bool uni = (a.R1 == 1 || a.div1 % 32 == 0) && (a.Rd == 1 || a.divd % 32 == 0);
     const bool endy = ((a.n_pre + 1 + a.n_post) & 1) != 0;
-    if (MODA_BF16_CB128 > 1 && uni && !endy && a.M >= 256 * 512 && a.n_live == nullptr)
-        return launch_p<128, P, (MODA_BF16_CB128 > 1 ? MODA_BF16_CB128 : 1), MODA_BF16_WAVES, false, true, false, 0, 4>(a, st);
-    return launch<128, P, MODA_BF16_CB, MODA_BF16_WAVES>(a, st);
+    if (kBf16Cb128 > 1 && uni && !endy && a.M >= 256 * 512 && a.n_live == nullptr)
+        return launch_p<128, P, (kBf16Cb128 > 1 ? kBf16Cb128 : 1), kBf16Waves, false, true, false, 0, 4>(a, st);
+    return launch<128, P, kBf16Cb, kBf16Waves>(a, st);
 }
 
 static int dispatch(const moda_mlp_desc* d, const MlpArgs& a, hipStream_t st) {
@@ -2193,37 +1910,37 @@ static int dispatch(const moda_mlp_desc* d, const MlpArgs& a, hipStream_t st) {
     if (hx && d->W != 256) return MODA_ESHAPE;
     const bool bf16 = (d->flags & MODA_MLP_BF16) != 0;
     if (d->flags & MODA_MLP_BF16X3) {
-        if (d->W == 256) return launch<256, PrecBF16x3, 1, MODA_X3_WAVES256>(a, st);
-        if (d->W == 128) return launch<128, PrecBF16x3, 1, MODA_X3_WAVES128>(a, st);
-        return launch<64, PrecBF16x3, 1, MODA_X3_WAVES>(a, st);
+        if (d->W == 256) return launch<256, PrecBF16x3, 1, kX3Waves256>(a, st);
+        if (d->W == 128) return launch<128, PrecBF16x3, 1, kX3Waves128>(a, st);
+        return launch<64, PrecBF16x3, 1, kX3Waves>(a, st);
     }
     if (d->flags & MODA_MLP_F16) {
         const char* agpr_env16 = getenv("MODA_MLP_AGPR");        // (read per call, as for bf16 below)
-        const int agpr16 = agpr_env16 ? atoi(agpr_env16) : MODA_MLP_AGPR_DEFAULT;
+        const int agpr16 = agpr_env16 ? atoi(agpr_env16) : kMlpAgprDefault;
         if (d->W == 256 && hx && agpr16 && a.n_live == nullptr) {            // the four-wave AGPR form (PrecF16A), uniform column blocks only
             const bool uni = (a.R1 == 1 || a.div1 % 32 == 0) && (a.Rd == 1 || a.divd % 32 == 0);
             const bool endy = ((a.n_pre + 1 + a.n_post) & 1) != 0;
-            if (uni) return endy ? launch_p<256, PrecF16A, 2, 4, true, true, false, 0, MODA_RING, false, true>(a, st)
-                                 : launch_p<256, PrecF16A, 2, 4, false, true, false, 0, MODA_RING, false, true>(a, st);
+            if (uni) return endy ? launch_p<256, PrecF16A, 2, 4, true, true, false, 0, kRingDepth, false, true>(a, st)
+                                 : launch_p<256, PrecF16A, 2, 4, false, true, false, 0, kRingDepth, false, true>(a, st);
         }
-        if (d->W == 256 && hx) return launch<256, PrecF16, MODA_BF16_CB, MODA_BF16_WAVES, 0, MODA_RING, true>(a, st);
-        if (d->W == 256) return launch<256, PrecF16, MODA_BF16_CB, MODA_BF16_WAVES>(a, st);
+        if (d->W == 256 && hx) return launch<256, PrecF16, kBf16Cb, kBf16Waves, 0, kRingDepth, true>(a, st);
+        if (d->W == 256) return launch<256, PrecF16, kBf16Cb, kBf16Waves>(a, st);
         if (d->W == 128) return wide128<PrecF16>(a, st);
-        return launch<64, PrecF16, MODA_BF16_CB64, (MODA_RESIDENT ? MODA_BF16_WAVES64 : MODA_BF16_WAVES)>(a, st);
+        return launch<64, PrecF16, kBf16Cb64, kBf16Waves64>(a, st);
     }
     if (bf16) {
         // MODA_MLP_AGPR=1: the four-wave, two-column-block form with the activations in AGPRs (PrecBF16A), uniform column blocks
         // only.  A run-time switch so that both forms can be timed in one process (interleaved A/B on one box).
         const char* agpr_env = getenv("MODA_MLP_AGPR");            // (read per call: both forms in one process)
-        const int agpr = agpr_env ? atoi(agpr_env) : MODA_MLP_AGPR_DEFAULT;
+        const int agpr = agpr_env ? atoi(agpr_env) : kMlpAgprDefault;
         if (d->W == 256 && agpr && a.n_live == nullptr) {
             const bool uni = (a.R1 == 1 || a.div1 % 32 == 0) && (a.Rd == 1 || a.divd % 32 == 0);
             const bool endy = ((a.n_pre + 1 + a.n_post) & 1) != 0;
             if (uni) return endy ? launch_p<256, PrecBF16A, 2, 4, true, true>(a, st) : launch_p<256, PrecBF16A, 2, 4, false, true>(a, st);
         }
-        if (d->W == 256) return launch<256, PrecBF16, MODA_BF16_CB, MODA_BF16_WAVES>(a, st);
+        if (d->W == 256) return launch<256, PrecBF16, kBf16Cb, kBf16Waves>(a, st);
         if (d->W == 128) return wide128<PrecBF16>(a, st);
-        return launch<64, PrecBF16, MODA_BF16_CB64, (MODA_RESIDENT ? MODA_BF16_WAVES64 : MODA_BF16_WAVES)>(a, st);
+        return launch<64, PrecBF16, kBf16Cb64, kBf16Waves64>(a, st);
     }
     if (d->W == 256) return launch<256, PrecF32, 1, 4>(a, st);
     if (d->W == 128) return launch<128, PrecF32, 1, 4>(a, st);
@@ -2358,8 +2075,8 @@ extern "C" int moda_mlp_composite_fwd(const moda_mlp_desc* d, const void* wstrea
     a.comp_out = CompOut{rgb, nullptr, depth, sil, weights, visibility, nullptr, cyc_out, nullptr};
     const bool endy = ((a.n_pre + 1 + a.n_post) & 1) != 0;
     hipStream_t st = (hipStream_t)stream;
-    return endy ? launch_p<256, PrecBF16, 1, 8, true, true, false, 0, MODA_RING, true>(a, st)
-                : launch_p<256, PrecBF16, 1, 8, false, true, false, 0, MODA_RING, true>(a, st);
+    return endy ? launch_p<256, PrecBF16, 1, 8, true, true, false, 0, kRingDepth, true>(a, st)
+                : launch_p<256, PrecBF16, 1, 8, false, true, false, 0, kRingDepth, true>(a, st);
 }
 
 extern "C" int moda_mlp_warp_fwd(const moda_mlp_desc* d, const void* wstream, const float* bias, const float* xyz,
@@ -2394,20 +2111,20 @@ extern "C" int moda_mlp_warp_fwd(const moda_mlp_desc* d, const void* wstream, co
         a.rows_at_runs = 1;
     }
     a.run_start = (const int*)run_start;
-    constexpr int NW = MODA_RESIDENT ? MODA_BF16_WAVES64 : MODA_BF16_WAVES;
+    constexpr int NW = kBf16Waves64;
     const bool endy = ((a.n_pre + 1 + a.n_post) & 1) != 0;
     hipStream_t st = (hipStream_t)stream;
     if (d->flags & MODA_MLP_F16_HEADS)
-        return endy ? launch_p<64, PrecF16, MODA_BF16_CB64, NW, true, true, true, 0, MODA_RING, false, true>(a, st)
-                    : launch_p<64, PrecF16, MODA_BF16_CB64, NW, false, true, true, 0, MODA_RING, false, true>(a, st);
+        return endy ? launch_p<64, PrecF16, kBf16Cb64, NW, true, true, true, 0, kRingDepth, false, true>(a, st)
+                    : launch_p<64, PrecF16, kBf16Cb64, NW, false, true, true, 0, kRingDepth, false, true>(a, st);
     if (d->flags & MODA_MLP_F16)
-        return endy ? launch_p<64, PrecF16, MODA_BF16_CB64, NW, true, true, true>(a, st)
-                    : launch_p<64, PrecF16, MODA_BF16_CB64, NW, false, true, true>(a, st);
+        return endy ? launch_p<64, PrecF16, kBf16Cb64, NW, true, true, true>(a, st)
+                    : launch_p<64, PrecF16, kBf16Cb64, NW, false, true, true>(a, st);
     if (d->flags & MODA_MLP_BF16X3)      // the parity-grade form: split-bf16 network, same tail (round 4)
-        return endy ? launch_p<64, PrecBF16x3, 1, MODA_X3_WAVES, true, true, true>(a, st)
-                    : launch_p<64, PrecBF16x3, 1, MODA_X3_WAVES, false, true, true>(a, st);
-    return endy ? launch_p<64, PrecBF16, MODA_BF16_CB64, NW, true, true, true>(a, st)
-                : launch_p<64, PrecBF16, MODA_BF16_CB64, NW, false, true, true>(a, st);
+        return endy ? launch_p<64, PrecBF16x3, 1, kX3Waves, true, true, true>(a, st)
+                    : launch_p<64, PrecBF16x3, 1, kX3Waves, false, true, true>(a, st);
+    return endy ? launch_p<64, PrecBF16, kBf16Cb64, NW, true, true, true>(a, st)
+                : launch_p<64, PrecBF16, kBf16Cb64, NW, false, true, true>(a, st);
 }
 
 extern "C" int moda_mlp_dump_fwd(const moda_mlp_desc* d, const void* wstream, const float* bias, const float* xyz,
@@ -2430,30 +2147,17 @@ extern "C" int moda_mlp_dump_fwd(const moda_mlp_desc* d, const void* wstream, co
     a.dump_dd = dump_dd;
     a.dump_bf16 = (d->reserved & MODA_MLP_DUMP_BF16) != 0;
     hipStream_t st = (hipStream_t)stream;
-#ifndef MODA_DUMP_MODE
-#define MODA_DUMP_MODE 3           // bf16 dumps: 3 through the per-wave LDS transpose, 2 lane-pair swap + 16-byte scattered stores
-#endif
     if (a.dump_bf16) {
         // 8 x 256: lane-pair swap + 16-byte stores with the usual 8 waves (0.80 ms; the LDS route needs the waves halved for
         // its buffers and loses more to the ring than the wider stores gain: 1.16 ms).  Narrower nets: through LDS.
         // (measured for 8 x 256, all 0.79-0.83 ms: the pair-swap form; one-tile LDS transposes with all 8 waves and a 5-deep
-        //  ring, -DMODA_DUMP_MODE256=4; the ring's counted wait relaxed by 4 or 8 operations as an experiment.  Neither the
-        //  width of the stores nor the wait is what bounds this kernel.)
-#ifndef MODA_DUMP_MODE256
-#define MODA_DUMP_MODE256 2
-#endif
-#if MODA_DUMP_MODE256 == 4
-        if (d->W == 256) return launch<256, PrecBF16, MODA_BF16_CB, MODA_BF16_WAVES, 4, MODA_RING - 1>(a, st);
-#endif
-        if (d->W == 256) return launch<256, PrecBF16, MODA_BF16_CB, MODA_BF16_WAVES, 2>(a, st);
-        if (MODA_DUMP_MODE == 3) {
-            if (d->W == 128) return launch<128, PrecBF16, MODA_BF16_CB, 4, 3>(a, st);
-            return launch<64, PrecBF16, MODA_BF16_CB64, 8, 3>(a, st);
-        }
-        if (d->W == 128) return launch<128, PrecBF16, MODA_BF16_CB, MODA_BF16_WAVES, 2>(a, st);
-        return launch<64, PrecBF16, MODA_BF16_CB64, (MODA_RESIDENT ? MODA_BF16_WAVES64 : MODA_BF16_WAVES), 2>(a, st);
+        //  ring; the ring's counted wait relaxed by 4 or 8 operations as an experiment.  Neither the width of the stores nor
+        //  the wait is what bounds this kernel.)
+        if (d->W == 256) return launch<256, PrecBF16, kBf16Cb, kBf16Waves, 2>(a, st);
+        if (d->W == 128) return launch<128, PrecBF16, kBf16Cb, 4, 3>(a, st);
+        return launch<64, PrecBF16, kBf16Cb64, 8, 3>(a, st);
     }
-    if (d->W == 256) return launch<256, PrecBF16, MODA_BF16_CB, MODA_BF16_WAVES, 1>(a, st);
-    if (d->W == 128) return launch<128, PrecBF16, MODA_BF16_CB, MODA_BF16_WAVES, 1>(a, st);
-    return launch<64, PrecBF16, MODA_BF16_CB64, (MODA_RESIDENT ? MODA_BF16_WAVES64 : MODA_BF16_WAVES), 1>(a, st);
+    if (d->W == 256) return launch<256, PrecBF16, kBf16Cb, kBf16Waves, 1>(a, st);
+    if (d->W == 128) return launch<128, PrecBF16, kBf16Cb, kBf16Waves, 1>(a, st);
+    return launch<64, PrecBF16, kBf16Cb64, kBf16Waves64, 1>(a, st);
 }

@@ -288,13 +288,8 @@ DEVINL float prep_logit(const float* __restrict__ P, float px, float py, float p
 // quaternion is accumulated under the same rescaling.  When every lane of a wave belongs to one ray
 // (S a multiple of 64, or simply a long ray) the per-ray bone data is addressed through a wave-uniform
 // pointer, which turns those loads into scalar loads.
-#ifndef MODA_WARP_G
-#define MODA_WARP_G 5
-#endif
-#ifndef MODA_WARP_SPT
-#define MODA_WARP_SPT 4            // samples per thread of the hot warp configuration (4, 2, or 1 = one-sample kernel only)
-#endif
-constexpr int kG = MODA_WARP_G;   // bones per online-softmax group
+constexpr int kG = 5;             // bones per online-softmax group
+constexpr int kWarpSpt = 4;       // samples per thread of the hot warp configuration (4, 2, or 1 = one-sample kernel only)
 
 // STAGE: the sample's row of B logits / skinning weights lives in LDS (`trow`, staged and written back by the kernel with
 // coalesced accesses); without it the row is read and written in place in global memory, B floats per lane at a B-float
@@ -331,11 +326,7 @@ DEVINL void warp_body(const float* __restrict__ prep, int bones_per_ray, int rps
         float l[kG];
 #pragma unroll
         for (int j = 0; j < kG; ++j) l[j] = dnext[j];
-#ifdef MODA_ABL_DSKIN_RT
-        if (dskin) {
-#else
         if (HAS_DSKIN) {   // compile-time: a run-time test here would put the prefetch in its own block, waited for at the join
-#endif
 #pragma unroll
             for (int j = 0; j < kG; ++j)
                 dnext[j] = STAGE ? trow[min(g0 + kG + j, B - 1)] : dskin[ds_base + (long long)min(g0 + kG + j, B - 1) * ds_step];
@@ -1485,10 +1476,10 @@ extern "C" int moda_warp_frames_fwd(const float* bones, int32_t bones_per_set, c
     hipLaunchKernelGGL(dq_prep_kernel, dim3(nblocks(nsets * B)), dim3(kBlock), 0, ST(stream), dq, invert, nsets * B, dqp);
     dim3 grid(nblocks(N * S)), block(kBlock);
     const bool al16 = ((((uintptr_t)dskin) | ((uintptr_t)pts)) & 15) == 0;
-    if (!skin_out && dskin && dskin_bns && S % 256 == 0 && al16 && MODA_WARP_SPT == 4)
+    if (!skin_out && dskin && dskin_bns && S % 256 == 0 && al16 && kWarpSpt == 4)
         hipLaunchKernelGGL((warp_multi_kernel<4>), dim3(nblocks(N * S / 4)), block, 0, ST(stream), prep, bones_per_set, rps, dqp,
                            pts, pts_tf, dskin, skin_aux, (long long)N, (long long)S, B, xyz_out, cyc_ref, cyc_out);
-    else if (!skin_out && dskin && dskin_bns && S % 128 == 0 && al16 && MODA_WARP_SPT >= 2)
+    else if (!skin_out && dskin && dskin_bns && S % 128 == 0 && al16 && kWarpSpt >= 2)
         hipLaunchKernelGGL((warp_multi_kernel<2>), dim3(nblocks(N * S / 2)), block, 0, ST(stream), prep, bones_per_set, rps, dqp,
                            pts, pts_tf, dskin, skin_aux, (long long)N, (long long)S, B, xyz_out, cyc_ref, cyc_out);
     else if (skin_out && warp_can_stage(B, dskin_bns))

@@ -233,11 +233,9 @@ DEVINL float4 g2_load_kslow(const float* __restrict__ base, long long ld, int k,
 // ragged ones (K not a multiple of 8, second A source, row bias, sigmoid).
 // ST: the storage-type flags of Gemm2Args are honoured (bf16 mode only); without it every operand is fp32 in memory and the
 // element accessors fold to plain loads / stores.
-#ifndef MODA_G2_OCC128
-#define MODA_G2_OCC128 2
-#endif
+constexpr int kG2Occ128 = 2;      // workgroups per CU the 128-column split-bf16 forms are bounded for
 template <int BN, bool AK, bool BK, int BF = 0, bool ST = false>
-__global__ __launch_bounds__(256, (BN == 128 && BF >= 2) ? MODA_G2_OCC128 : 3) void gemm2_kernel(Gemm2Args a) {
+__global__ __launch_bounds__(256, (BN == 128 && BF >= 2) ? kG2Occ128 : 3) void gemm2_kernel(Gemm2Args a) {
     static_assert(BF == 1 || !ST, "storage types belong to the bf16 mode");
     const int a_bf = ST ? a.a_bf : 0, b_bf = ST ? a.b_bf : 0, c_bf = ST ? a.c_bf : 0, m_bf = ST ? a.m_bf : 0;
     constexpr int TM = (BN == 128) ? 2 : 1;
@@ -260,14 +258,12 @@ __global__ __launch_bounds__(256, (BN == 128 && BF >= 2) ? MODA_G2_OCC128 : 3) v
     // Placement is a speed hint only; any block -> tile bijection is correct.
     const unsigned lid = blockIdx.x;
     unsigned bx = lid % a.gx, by = lid / a.gx;
-#ifndef MODA_ABL_NO_XCD
     if (a.gx > 1 && (a.gy & 7) == 0) {
         const unsigned span = 8 * a.gx;
         const unsigned r = lid % span;
         bx = r >> 3;
         by = (lid / span) * 8 + (r & 7);
     }
-#endif
     const long long m0 = (long long)by * G2_BM, n0 = (long long)bx * BN;
     const int kbeg = blockIdx.z * a.ksplit;
     const int kend = min(a.K, kbeg + a.ksplit);
