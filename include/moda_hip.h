@@ -1315,6 +1315,44 @@ int moda_nvs_assemble(const int32_t* rank, int64_t B, int64_t S, int64_t n, cons
                       const float* sil_in, const float* vis_in, float* rgb, float* depth, float* sil, float* vis, uint8_t* rgb8,
                       uint8_t* sil8, uint8_t* vis8, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Mesh sequence export: the rest mesh warped to every frame at once, view-dependent vertex colours, bones as ellipsoids, skin
+ * colours (nnutils/train_utils.py:522-593, utils/io.py:51-78 and :559-582; moda_amd/csrc/animate_kernels.hip; purely additive
+ * entries of ABI 11: no existing signature changed, so moda_abi_version() stays 11).  Nothing allocates, synchronises or reads
+ * back, every launch goes to `stream`.  No atomics: the same bits on every run.
+ * ------------------------------------------------------------------------ */
+#define MODA_ANIM_BLOCK 256          /* lanes (= vertices) of a workgroup of moda_dqs_frames */
+#define MODA_ANIM_FRAME_TILE 16      /* frames whose dual quaternions a workgroup holds in LDS at a time */
+#define MODA_ANIM_MAX_BONES 64       /* the largest B moda_dqs_frames is instantiated for (weights live in registers) */
+
+/* moda_dqs_frames: dqs_blend_skinning_chunk (geom_utils.py:457-493) with frame-independent weights.  dq (F,B,8) dual quaternions
+ * (16-byte aligned), skin (V,B), pts (V,3) -> out (F,V,3).  Per frame f and vertex v: bl = sum_b skin[v,b] dq[f,b] in increasing b
+ * (fma), c = bl / |bl[:4]|, out = p + 2 d0 x (d0 x p + a0 p) + 2 (a0 de - ae d0 + d0 x de).  One lane per vertex (weights and point
+ * in registers), frames walked in tiles of MODA_ANIM_FRAME_TILE held in LDS; frame_splits = the number of workgroups that share
+ * the tiles of one vertex block (0: chosen from the sizes).  A frame's row has the same bits for every F, every position of the
+ * frame in dq and every frame_splits.  A non-finite input reaches only its own vertex's (a weight or point) or frame's (a dual
+ * quaternion) outputs; |bl[:4]| == 0 gives NaN there.  MODA_ESHAPE: a size < 1 or >= 2^31, B > MODA_ANIM_MAX_BONES,
+ * frame_splits < 0.  MODA_EINVAL: NULL, dq not 16-byte aligned. */
+int moda_dqs_frames(const float* dq, const float* skin, const float* pts, int64_t F, int64_t V, int32_t B, int32_t frame_splits,
+                    float* out, void* stream);
+
+/* moda_color_dirs: the per-sample `dir_src` rows of get_vertex_colors (utils/io.py:559-582) for Fc frames of V vertices, one
+ * thread per output float: out (Fc V, 3 (1 + 2 n_freq) + Ce) = [Embedding(d) | env (Fc,Ce) row of the frame], d =
+ * (verts (Fc,V,3) - cam (Fc,3)) / max(|.|, 1e-12), or d = (0, 0, -1) when verts and cam are both NULL; Embedding as
+ * moda_embed_fwd: [d, window[k] sin(2^k d), window[k] cos(2^k d)]_k.  MODA_ESHAPE: a size < 1, n_freq outside 0..16, Ce outside
+ * 0..65536, too many outputs.  MODA_EINVAL: NULL, or only one of verts and cam. */
+int moda_color_dirs(const float* verts, const float* cam, const float* env, int64_t Fc, int64_t V, int32_t n_freq, const float* window,
+                    int32_t Ce, float* out, void* stream);
+
+/* moda_bone_ellipsoids: save_bones (utils/io.py:51-78) for n_bones bones (n_bones,10) = [centre | quaternion, real first | log
+ * scale] and a template tmpl (Nv,3): out (n_bones, Nv, 3) = centre + R(q / |q|) (tmpl / exp(scale)), one thread per output vertex.
+ * MODA_ESHAPE: a size < 1 or too large.  MODA_EINVAL: NULL. */
+int moda_bone_ellipsoids(const float* bones, int64_t n_bones, const float* tmpl, int32_t Nv, float* out, void* stream);
+
+/* moda_skin_colors: out (V,3) = sum_b palette (B,3)[b] skin (V,B)[v,b] in increasing b (fma) (train_utils.py:587).
+ * MODA_ESHAPE: a size < 1, V >= 2^31, B > 65536.  MODA_EINVAL: NULL. */
+int moda_skin_colors(const float* skin, const float* palette, int64_t V, int32_t B, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

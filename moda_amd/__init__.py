@@ -56,3 +56,6 @@ from . import warmup  # noqa: F401
 from .warmup import forward_warmup_shape, forward_warmup_rootmlp, preset_root_rotations, WarmupHarness  # noqa: F401
 from . import nvs  # noqa: F401
 from .nvs import mask_to_pixels, construct_rays_nvs, render_nvs, crop_short_edge, assemble_frames, NVSFrames  # noqa: F401
+from . import animate  # noqa: F401
+from .animate import (skin_weights, displaced_vertices, warp_fw_frames, vertex_colors_frames, bone_ellipsoids,  # noqa: F401
+                      skin_colors, export_sequence, MeshSequence, write_obj, read_obj)

@@ -188,6 +188,11 @@ _SIGNATURES = {
     "moda_mask_compact": (_c.c_int, [_P, _I32, _I64, _I64, _P, _P, _P, _P, _P, _P]),
     "moda_nvs_rays": (_c.c_int, [_P, _P, _I64, _I64, _I64] + [_P] * 10 + [_P, _I64, _P] * 3 + [_P]),
     "moda_nvs_assemble": (_c.c_int, [_P, _I64, _I64, _I64] + [_P] * 12),
+    # mesh sequence export: all-frames DQS warp, colour rows, bone ellipsoids, skin colours (animate_kernels.hip): additive, the ABI stays 11
+    "moda_dqs_frames": (_c.c_int, [_P, _P, _P, _I64, _I64, _I32, _I32, _P, _P]),
+    "moda_color_dirs": (_c.c_int, [_P, _P, _P, _I64, _I64, _I32, _P, _I32, _P, _P]),
+    "moda_bone_ellipsoids": (_c.c_int, [_P, _I64, _P, _I32, _P, _P]),
+    "moda_skin_colors": (_c.c_int, [_P, _P, _I64, _I32, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
