@@ -1353,6 +1353,46 @@ int moda_bone_ellipsoids(const float* bones, int64_t n_bones, const float* tmpl,
  * MODA_ESHAPE: a size < 1, V >= 2^31, B > 65536.  MODA_EINVAL: NULL. */
 int moda_skin_colors(const float* skin, const float* palette, int64_t V, int32_t B, float* out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The pose CNN in inference mode: the ResNet-18 trunk, the tail conv block and the input / output reshuffles of Encoder
+ * (nnutils/nerf.py:513-573) as extract_cams runs it (nnutils/train_utils.py:393-453; moda_amd/csrc/posecnn_kernels.hip; purely
+ * additive entries of ABI 11: no existing signature changed, so moda_abi_version() stays 11).  fp32, activations NHWC.  Nothing
+ * allocates, synchronises or reads back, every launch goes to `stream`.  No split of a reduction and no atomics: the same bits
+ * on every run, and a frame has the same bits alone and inside any batch.
+ * ------------------------------------------------------------------------ */
+#define MODA_CONV_K_CHUNK 16         /* channels of one tap staged per step: Cin must be a multiple */
+#define MODA_CONV_ACT_NONE 0
+#define MODA_CONV_ACT_RELU 1
+#define MODA_CONV_ACT_LEAKY 2        /* LeakyReLU(0.2) */
+#define MODA_CONV_TILE_AUTO 0        /* 64 x 64 where that gives >= 256 workgroups, else 32 x 32 */
+#define MODA_CONV_TILE_32 1          /* one wave per workgroup: 32 pixels x 32 output channels */
+#define MODA_CONV_TILE_64 2          /* 2 x 2 waves: 64 pixels x 64 output channels */
+
+/* moda_conv2d_nhwc: in (B,H,W,Cin), w (Cout,kh,kw,Cin), bias (Cout), res (B,Ho,Wo,Cout) or NULL -> out (B,Ho,Wo,Cout),
+ * Ho = (H + 2 pad - kh) / stride + 1.  out = act((sum_k in w + bias) + res): the sum is ONE fp32 fma chain from 0 over
+ * k = (ky, kx, c) ascending (v_mfma_f32_32x32x2_f32), a tap outside the image contributing a zero operand; the additions and the
+ * activation are single fp32 operations.  The bits of an output element do not depend on `tile`, B, or the element's place.
+ * `in` and `w` 16-byte aligned.  MODA_ESHAPE: a size < 1, Cin % MODA_CONV_K_CHUNK != 0, kh | kw | stride > 16, pad >= kh | kw,
+ * the padded image smaller than the kernel, a size too large.  MODA_EINVAL: NULL, alignment, an unknown act or tile. */
+int moda_conv2d_nhwc(const float* in, const float* w, const float* bias, const float* res, float* out, int64_t B, int64_t H,
+                     int64_t W, int64_t Cin, int64_t Cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad, int32_t act,
+                     int32_t tile, void* stream);
+/* the tile form moda_conv2d_nhwc takes for M = B Ho Wo pixels (MODA_CONV_TILE_32 | _64); a forced `tile` is returned as is */
+int32_t moda_conv2d_tile(int64_t M, int64_t Cout, int32_t tile);
+
+/* moda_maxpool3x3s2_nhwc: F.max_pool2d(., 3, 2, 1) over in (B,H,W,C) -> out (B,(H-1)/2+1,(W-1)/2+1,C): the padding is -inf, a NaN
+ * wins.  C % 4 == 0, both 16-byte aligned.  MODA_ESHAPE / MODA_EINVAL as above. */
+int moda_maxpool3x3s2_nhwc(const float* in, int64_t B, int64_t H, int64_t W, int64_t C, float* out, void* stream);
+
+/* moda_posecnn_input: src (B,C,H,W) -> dst (B,H,W,Cp), Cp >= C, channels C .. Cp-1 zero; normalize != 0: every pixel's C values
+ * divided by max(|.|_2, 1e-12) (F.normalize(., 2, 1), moda.py:1399), norm and quotient formed in float64 and rounded once: an
+ * all-zero pixel stays zero. */
+int moda_posecnn_input(const float* src, int64_t B, int64_t C, int64_t H, int64_t W, int64_t Cp, int32_t normalize, float* dst,
+                       void* stream);
+
+/* moda_posecnn_tail: x (B,P,C) -> out (B,C), the maximum over the P positions (max_pool2d over the whole map); a NaN wins. */
+int moda_posecnn_tail(const float* x, int64_t B, int64_t P, int64_t C, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,10 @@ from .loss_utils import shape_init_loss, rtk_loss, compute_root_sm_loss, compute
 from .geom_utils import matrix_to_quaternion  # noqa: F401
 from . import warmup  # noqa: F401
 from .warmup import forward_warmup_shape, forward_warmup_rootmlp, preset_root_rotations, WarmupHarness  # noqa: F401
+from . import pose_cnn  # noqa: F401
+from .pose_cnn import Encoder, ResNetConv  # noqa: F401
+from .checkpoint import build_pose_cnn  # noqa: F401
+from .warmup import extract_cams  # noqa: F401
 from . import nvs  # noqa: F401
 from .nvs import mask_to_pixels, construct_rays_nvs, render_nvs, crop_short_edge, assemble_frames, NVSFrames  # noqa: F401
 from . import animate  # noqa: F401

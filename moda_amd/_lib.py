@@ -193,6 +193,12 @@ _SIGNATURES = {
     "moda_color_dirs": (_c.c_int, [_P, _P, _P, _I64, _I64, _I32, _P, _I32, _P, _P]),
     "moda_bone_ellipsoids": (_c.c_int, [_P, _I64, _P, _I32, _P, _P]),
     "moda_skin_colors": (_c.c_int, [_P, _P, _I64, _I32, _P, _P]),
+    # the pose CNN in inference mode: implicit-GEMM convolution, max pool, input and tail reshuffles (posecnn_kernels.hip): additive, the ABI stays 11
+    "moda_conv2d_nhwc": (_c.c_int, [_P] * 5 + [_I64] * 5 + [_I32] * 6 + [_P]),
+    "moda_conv2d_tile": (_I32, [_I64, _I64, _I32]),
+    "moda_maxpool3x3s2_nhwc": (_c.c_int, [_P, _I64, _I64, _I64, _I64, _P, _P]),
+    "moda_posecnn_input": (_c.c_int, [_P, _I64, _I64, _I64, _I64, _I64, _I32, _P, _P]),
+    "moda_posecnn_tail": (_c.c_int, [_P, _I64, _I64, _I64, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -71,10 +71,43 @@ def build_root_pose(states, data_offset, device='cuda'):
         m = RTExplicit(sd['se3'].shape[0], delta=sd['se3'].shape[1] == 6, rand=False)
     else:
         raise NotImplementedError("build_root_pose: no `nerf_root_rts.base_rt.se3` (expmlp) or `nerf_root_rts.se3` (exp) in the "
-                                  "state dict; the `mlp` and `cnn` bases are not rebuilt from checkpoints")
+                                  "state dict; the `mlp` basis is not rebuilt from checkpoints, and the `cnn` basis (a PoseNet "
+                                  "file) is build_pose_cnn's")
     m.load_state_dict(sd, strict=True)
     ks = s.get('ks_param')
     return {'nerf_root_rts': m.to(device), 'ks_param': None if ks is None else torch.nn.Parameter(ks.to(device))}
+
+
+POSE_CNN_PREFIXES = ('module.nerf_root_rts', 'module.dp_root_rts')
+
+
+def build_pose_cnn(states, prefix='module.nerf_root_rts', device='cuda'):
+    """states (a PoseNet state dict, mesh_material/posenet/*.pth as warmup_pose loads it, train_utils.py:899-903) ->
+    nn.Sequential(Encoder((112, 112), in_channels read off conv1), RTHead(use_quat=True, D=1, 128 -> 7)) in eval mode on `device`.
+    `prefix` is stripped as the reference's rm_module_prefix does; keys under `module.dp_root_rts` and unprefixed keys load too.
+    Unlike the reference's strict=False, a missing or an unexpected key is an error that names it."""
+    from .feeders import RTHead
+    from .pose_cnn import Encoder
+    sd = {}
+    for k, v in states.items():
+        for p in dict.fromkeys((prefix,) + POSE_CNN_PREFIXES):
+            if p and k.startswith(p + '.'):
+                k = k[len(p) + 1:]
+                break
+        sd[k] = v.float() if torch.is_tensor(v) and v.is_floating_point() else v
+    w = sd.get('0.resnet_conv.resnet.conv1.weight')
+    if w is None or w.dim() != 4:
+        raise KeyError("build_pose_cnn: no `0.resnet_conv.resnet.conv1.weight` in the state dict (after stripping "
+                       f"{prefix!r}): not a PoseNet nn.Sequential(Encoder, RTHead)")
+    m = torch.nn.Sequential(Encoder((112, 112), in_channels=w.shape[1], out_channels=128),
+                            RTHead(use_quat=True, D=1, in_channels_xyz=128, in_channels_dir=0, out_channels=7, raw_feat=True))
+    want = set(m.state_dict().keys())
+    missing, extra = sorted(want - set(sd)), sorted(set(sd) - want)
+    if missing or extra:
+        raise KeyError(f"build_pose_cnn: the state dict does not match nn.Sequential(Encoder, RTHead): missing {missing[:8]}"
+                       f"{' ...' if len(missing) > 8 else ''}, unexpected {extra[:8]}{' ...' if len(extra) > 8 else ''}")
+    m.load_state_dict(sd, strict=True)
+    return m.to(device).eval()
 
 
 def build_models(states, device='cuda', data_offset=None, num_freqs=10):

@@ -3,7 +3,8 @@ table of all frames that the root-smoothness term reads (loss_utils.forward_loss
 (moda.py:1419-1447) the batch's (bs,4,4) poses with their intrinsics row, which geom_utils.prepare_ray_cams turns into what
 feeders.raycast takes.  The reference's methods read their inputs off the model object; here they are arguments.
 
-Whatever the module -- RTExpMLP (`expmlp`, the default), RTExplicit (`exp`), nn.Sequential(code, RTHead) (`mlp`) -- its tail,
+Whatever the module -- RTExpMLP (`expmlp`, the default), RTExplicit (`exp`), nn.Sequential(code, RTHead) (`mlp`),
+nn.Sequential(Encoder, RTHead) over image features (`cnn`, convert_root_pose(dp_feats=) only) -- its tail,
 refine_rt / create_base_se3 and the K row are ONE launch of moda_root_pose; the (bs,1,12) intermediate of the reference is not
 formed.  An id outside the table does not raise as the reference's indexing would: its row is NaN and it is counted in
 `nerf_root_rts.id_status` (device int32 [#frame ids refused, #data ids refused, 0, 0]; nothing is read back here)."""
@@ -11,29 +12,39 @@ import torch
 from torch import nn
 
 from .feeders import RAW_BASE, RAW_ROWS, FrameCode, RootPoseFn, RTExplicit, RTExpMLP, RTHead
+from .pose_cnn import Encoder
 
 
-def _parts(nerf_root_rts, frameid):
-    """-> (se3 table | None, delta rows | None) of a root-pose module for the frame ids."""
+def _parts(nerf_root_rts, frameid, dp_feats=None):
+    """-> (se3 table | None, delta rows | None) of a root-pose module for the frame ids (the `cnn` basis: for the images)."""
     m = nerf_root_rts
     if isinstance(m, RTExpMLP):
         return m.base_rt.se3, m.delta_rows(frameid)
     if isinstance(m, RTExplicit):
         return m.se3, None
     if isinstance(m, nn.Sequential) and len(m) == 2 and isinstance(m[1], RTHead):
+        if isinstance(m[0], Encoder):                            # root_basis='cnn' (moda.py:367-373, 1437-1438): frame_code = dp_feats
+            if dp_feats is None:
+                raise NotImplementedError("root poses: root_basis='cnn' -- the pose CNN `Encoder` reads image features, not frame "
+                                          "ids: convert_root_pose(..., dp_feats=) runs it; compute_rts refuses it as the "
+                                          "reference's does (moda.py:1489-1492)")
+            return None, m[1].raw(m[0](dp_feats))
         if not isinstance(m[0], (nn.Embedding, FrameCode)):      # anything else would be handed frame ids it cannot take
-            raise NotImplementedError(f"root poses: the `mlp` basis is nn.Sequential(nn.Embedding | FrameCode, RTHead); a first stage "
-                                      f"{type(m[0]).__name__} -- root_basis='cnn', the pose CNN `Encoder` over image features "
-                                      "(moda.py:367-373) -- is not implemented")
+            raise NotImplementedError(f"root poses: the `mlp` basis is nn.Sequential(nn.Embedding | FrameCode, RTHead) and the `cnn` "
+                                      f"basis nn.Sequential(moda_amd.Encoder, RTHead); a first stage {type(m[0]).__name__} is not "
+                                      "implemented (the pose CNN must be moda_amd.pose_cnn.`Encoder`)")
+        if dp_feats is not None:
+            raise ValueError(f"root poses: dp_feats goes with the `cnn` basis, nn.Sequential(Encoder, RTHead), not with a first stage "
+                             f"{type(m[0]).__name__}")
         return None, m[1].raw(m[0](frameid))
     if isinstance(m, RTHead):
         return None, m.raw(frameid)
     raise NotImplementedError(f"root poses: {type(m).__name__} is not a root-pose module (RTExpMLP, RTExplicit, Sequential(code, "
-                              "RTHead)); root_basis='cnn' needs the pose CNN `Encoder`, which is not implemented")
+                              "RTHead), Sequential(Encoder, RTHead))")
 
 
-def _tail(nerf_root_rts, frameid, rt_raw, obj_scale, ks, dataid, out_rows, root_opt):
-    se3, delta = _parts(nerf_root_rts, frameid) if root_opt else (None, None)
+def _tail(nerf_root_rts, frameid, rt_raw, obj_scale, ks, dataid, out_rows, root_opt, dp_feats=None):
+    se3, delta = _parts(nerf_root_rts, frameid, dp_feats) if root_opt else (None, None)
     mode = RAW_BASE if rt_raw is None else RAW_ROWS
     rtk, status = RootPoseFn.apply(se3, frameid, delta, rt_raw, mode, obj_scale if rt_raw is not None else 1.0, ks, dataid, out_rows)
     if nerf_root_rts is not None:
@@ -59,7 +70,8 @@ def _arange(n, device):
     return _ARANGE[k]
 
 
-def convert_root_pose(nerf_root_rts, frameid, dataid, ks_param, *, rtk=None, obj_scale=1.0, root_opt=True):
+def convert_root_pose(nerf_root_rts, frameid, dataid, ks_param, *, rtk=None, obj_scale=1.0, root_opt=True, dp_feats=None):
     """moda.py:1419-1447 -> (bs,4,4): the poses of the batch's frames with row 3 = ks_param[dataid].  rtk (bs, 3|4, 4): the
-    dataset's initial poses (use_cam), not modified; None: create_base_se3."""
-    return _tail(nerf_root_rts, frameid, rtk, obj_scale, ks_param, dataid, 4, root_opt)
+    dataset's initial poses (use_cam), not modified; None: create_base_se3.  dp_feats (bs,16,H,W): the frames' normalised
+    DensePose-CSE feature images, the `frame_code` of root_basis='cnn' (nn.Sequential(Encoder, RTHead), moda.py:1437-1438)."""
+    return _tail(nerf_root_rts, frameid, rtk, obj_scale, ks_param, dataid, 4, root_opt, dp_feats)

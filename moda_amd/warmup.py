@@ -7,11 +7,15 @@
                            second-order root smoothness;
   * preset_root_rotations  (nnutils/train_utils.py:662-666)  the table's rotations written into RTExpMLP's base quaternions;
   * WarmupHarness          (train_utils.py:845-869 warmup_shape)  the warmup_shape_ep x 200 optimiser steps of the shape stage,
-                           eager or as one captured graph replayed after each draw of the uniforms.
+                           eager or as one captured graph replayed after each draw of the uniforms;
+  * extract_cams           (train_utils.py:794-807 over eval_cam :393-453)  what warmup_pose(pose_cnn_path=...) is for: every frame's
+                           DensePose-CSE feature image through the PoseNet (pose_cnn.Encoder + RTHead, loaded by
+                           checkpoint.build_pose_cnn) into the frame table, in chunks.
 
 The reference's methods read their inputs off the model object; so do the two forward_warmup_* functions here (`model` is the
-DistributedDataParallel-wrapped or bare module).  warmup_pose / forward_warmup need the pose CNN `Encoder`, which is not
-implemented (root_pose refuses root_basis='cnn'); extract_cams is not implemented either."""
+DistributedDataParallel-wrapped or bare module).  TRAINING the pose CNN -- warmup_pose with warmup_pose_ep > 0 and no path,
+forward_warmup -- is not implemented (pose_cnn.Encoder refuses training mode), nor is the file and plot side of extract_cams
+(save_cams, align_sfm_sim3, visual_hull_align, process_so3_seq, render_root_txt, draw_cams)."""
 import numpy as np
 import torch
 
@@ -95,6 +99,60 @@ def preset_root_rotations(nerf_root_rts, rtk):
     with torch.no_grad():
         se3.data[:, 3:] = matrix_to_quaternion(rtk.detach()[:, :3, :3])
     return nerf_root_rts
+
+
+def extract_cams(pose_cnn, dp_feats, frameid, dataid, ks_param, kaug, state, *, dp_embed=None, dps=None, unc_filter=False, chunk=50,
+                 normalize=True, rt_raw=None):
+    """The loop of v2s_trainer.extract_cams / eval_cam (train_utils.py:794-807, 393-453) up to the filled frame table: every
+    frame's DensePose-CSE feature image through the PoseNet `pose_cnn` = nn.Sequential(Encoder, RTHead) in chunks of `chunk` frames
+    (the reference: 50), the result written into `state` (a FrameState) as save_latest_vars does.
+
+    dp_feats (N,16,H,W) fp32 on the device; frameid (N,) the frames' rows in the tables (video offset included); dataid (N,);
+    ks_param (n_videos,4); kaug (N,4).  Per chunk: F.normalize(dp_feats, 2, 1) (moda.py:1399; normalize=False: the features are
+    normalised already), with unc_filter ood_check_cse against dp_embed (V,16) and dps (N,H',W'), convert_root_pose(dp_feats=) on
+    create_base_se3 (use_cam=False, as warmup_pose sets it), save_latest_vars.  rt_raw (N,3,4): what the table's rt_raw rows
+    receive; None: the CNN's poses, which is what the reference's table holds once save_cams has run (train_utils.py:789).
+
+    -> (rtk (N,4,4), is_valid (N,) bool, err_valid (N,) fp32), device tensors; nothing is read back.  The module must be in eval
+    mode (checkpoint.build_pose_cnn returns it so).  A frame's result does not depend on `chunk`.  The file and plot side of the
+    reference's extract_cams (save_cams, align_sfm_sim3, visual_hull_align, process_so3_seq, render_root_txt, draw_cams) is not
+    implemented: the caller reads the returned tensors."""
+    from types import SimpleNamespace
+
+    from .cse import ood_check_cse
+    from .frame_state import save_latest_vars
+    from .pose_cnn import normalize_feats
+    from .root_pose import convert_root_pose
+    if not isinstance(state, FrameState):
+        raise TypeError("extract_cams: state must be a moda_amd.FrameState")
+    if not torch.is_tensor(dp_feats) or dp_feats.dim() != 4:
+        raise ValueError("extract_cams: dp_feats must be a (N, C, H, W) tensor")
+    N, chunk = dp_feats.shape[0], int(chunk)
+    if chunk < 1 or N < 1:
+        raise ValueError(f"extract_cams: {N} frames in chunks of {chunk}")
+    if unc_filter and (dp_embed is None or dps is None):
+        raise ValueError("extract_cams: unc_filter needs dp_embed (V,16) and dps (N,H,W)")
+    kaug = kaug.reshape(-1, 4)
+    for t, what in ((frameid, "frameid"), (dataid, "dataid"), (kaug, "kaug"), (rt_raw, "rt_raw"), (dps if unc_filter else None, "dps")):
+        if t is not None and t.shape[0] != N:
+            raise ValueError(f"extract_cams: {what} holds {t.shape[0]} entries for {N} frames")
+    dev = dp_feats.device
+    rtk_all = torch.empty((N, 4, 4), device=dev)
+    is_valid = torch.ones((N,), device=dev, dtype=torch.bool)
+    err_valid = torch.zeros((N,), device=dev)
+    with torch.no_grad():
+        for i in range(0, N, chunk):
+            sl = slice(i, min(i + chunk, N))
+            feats = dp_feats[sl]
+            if normalize:
+                feats = normalize_feats(feats)
+            if unc_filter:
+                is_valid[sl], err_valid[sl] = ood_check_cse(feats, dp_embed, dps[sl])
+            rtk = convert_root_pose(pose_cnn, frameid[sl], dataid[sl], ks_param, dp_feats=feats)
+            rtk_all[sl] = rtk
+            save_latest_vars(SimpleNamespace(rtk=rtk, kaug=kaug[sl], rt_raw=rtk[:, :3] if rt_raw is None else rt_raw[sl],
+                                             frameid=frameid[sl], latest_vars=state))
+    return rtk_all, is_valid, err_valid
 
 
 class WarmupHarness:
