@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("MODA_LIB_PATH") or BUILT_LIB
 # lane, this one 20; max-memory-clause 12.13), the other kernels of the file unchanged (A/B on one box, twice).
 FILE_FLAGS = {"mlp_fused.hip": ("-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp")}
 SOURCES = ("mlp_fused.hip", "render_kernels.hip", "train_kernels.hip", "gemm_bf16.hip", "gemm_x3.hip", "bwd64_chain.hip", "bwd256_fused.hip", "loss_kernels.hip", "prep_kernels.hip", "mesh_kernels.hip", "pointset_kernels.hip", "raster_kernels.hip", "bones_kernels.hip", "clip_kernels.hip", "lossasm_kernels.hip", "sinkdiv_kernels.hip", "rootpose_kernels.hip", "optim_kernels.hip", "pixsample_kernels.hip", "frames_kernels.hip", "cse_kernels.hip", "framepair_kernels.hip", "warmup_kernels.hip", "nvs_kernels.hip", "animate_kernels.hip", "posecnn_kernels.hip")
+HEADERS = (os.path.join(CSRC, "moda_dev.h"), os.path.join(CSRC, "mfma_tiles.h"), os.path.join(ROOT, "include", "moda_hip.h"))
 
 
 def _hipcc():
@@ -40,13 +41,13 @@ def _stamp_matches():
 
 
 def source_hash():
-    """sha256[:16] over everything that decides what the kernels are: the HIP sources, the two headers, the per-file flags.
+    """sha256[:16] over everything that decides what the kernels are: the HIP sources, the headers, the per-file flags.
     profiles/traffic.json is stamped with it by tools/pmc_summary.py, and bench.py reports `roofline.traffic` (HBM bytes from the
     PMC counters) only when the stamp equals the hash of the sources it runs from -- a profile of another build is labelled stale
     instead of passing as a measurement of this one."""
     import hashlib
     h = hashlib.sha256()
-    for f in [os.path.join(CSRC, x) for x in SOURCES + ("moda_dev.h",)] + [os.path.join(ROOT, "include", "moda_hip.h")]:
+    for f in [os.path.join(CSRC, x) for x in SOURCES] + list(HEADERS):
         h.update(os.path.basename(f).encode() + b"\0" + open(f, "rb").read())
     h.update(repr(sorted(FILE_FLAGS.items())).encode())
     return h.hexdigest()[:16]
@@ -56,19 +57,17 @@ def needs_build():
     if not os.path.exists(BUILT_LIB) or not _stamp_matches():
         return True
     t = os.path.getmtime(BUILT_LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + ("moda_dev.h",)] + [os.path.join(ROOT, "include", "moda_hip.h")]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + list(HEADERS)
     return any(os.path.getmtime(d) > t for d in deps)
 
 
 def build(force=False, verbose=True, jobs=None):
     """hipcc --offload-arch=gfx950 -shared -fPIC: one code object per source (compiled in parallel; an object is reused
-    when it is newer than its source, the header and the flags it was built with), linked into one .so."""
+    when it is newer than its source, the headers and the flags it was built with), linked into one .so."""
     if not force and not needs_build():
         return BUILT_LIB
     from concurrent.futures import ThreadPoolExecutor
     os.makedirs(LIB_DIR, exist_ok=True)
-    hdr = os.path.join(ROOT, "include", "moda_hip.h")
-    dev_hdr = os.path.join(CSRC, "moda_dev.h")
     extra = os.environ.get("MODA_HIPCC_FLAGS", "").split()
     stamp = os.path.join(LIB_DIR, "flags.txt")
     same_flags = _stamp_matches()
@@ -78,7 +77,7 @@ def build(force=False, verbose=True, jobs=None):
     def compile_one(s):
         src = os.path.join(CSRC, s)
         obj = os.path.join(LIB_DIR, s.replace(".hip", ".o"))
-        if not force and same_flags and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(dev_hdr)):
+        if not force and same_flags and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(f) for f in (src,) + HEADERS):
             return obj
         cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
                "-c", src, "-o", obj] + (list(FILE_FLAGS.get(s, ())) if not os.environ.get("MODA_NO_FILE_FLAGS") else []) + extra

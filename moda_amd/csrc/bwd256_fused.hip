@@ -31,13 +31,9 @@
 #include <atomic>
 
 #include "moda_hip.h"
-#include "moda_dev.h"
+#include "mfma_tiles.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MT = 64;                 // samples per tile
 constexpr int HI = 128;                // input columns per workgroup
@@ -67,20 +63,6 @@ struct B256Args {
 };
 
 DEVINL int fsw(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-DEVINL unsigned pk2(float lo, float hi) {
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-    const f32x2_ t = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2_));
-}
-DEVINL float bflo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-DEVINL float bfhi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-// bf16 > 0  <=>  its 16 bits, as a signed integer, > 0 (gemm_bf16.hip's mask rule)
-DEVINL unsigned keep(unsigned vw, unsigned mw) {
-    const unsigned lo = ((short)(mw & 0xffffu) > 0) ? 0x0000ffffu : 0u;
-    const unsigned hi = ((int)mw > 0xffff) ? 0xffff0000u : 0u;
-    return vw & (lo | hi);
-}
 
 template <int WD>
 __global__ __launch_bounds__(512, 1) void bwd256_kernel(B256Args a) {
@@ -220,7 +202,7 @@ __global__ __launch_bounds__(512, 1) void bwd256_kernel(B256Args a) {
                 for (int j = 0; j < 4; ++j) {
                     const uint2 mk = *(const uint2*)(St + xmk + 32 * mb * XROW + 16 * ((4 * ib + j) ^ fz));
                     *(uint2*)(Ow + 32 * mb * 64 + ost + 16 * (j ^ osw)) =
-                        make_uint2(keep(pk2(accx[mb][4 * j], accx[mb][4 * j + 1]), mk.x), keep(pk2(accx[mb][4 * j + 2], accx[mb][4 * j + 3]), mk.y));
+                        make_uint2(keep_pos(pk2(accx[mb][4 * j], accx[mb][4 * j + 1]), mk.x), keep_pos(pk2(accx[mb][4 * j + 2], accx[mb][4 * j + 3]), mk.y));
                 }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -241,7 +223,7 @@ __global__ __launch_bounds__(512, 1) void bwd256_kernel(B256Args a) {
         }
     } else {
         // ================= dW waves: dW[all 256 o][i-block ib] += dZ^T X over the tile's 64 samples ===========================
-        // transposing read (gemm_bf16.hip): lane (h, g & 1, q4, p4) supplies row 16u + 8h + q4 (+ 4 for the high half), elements
+        // transposing read (tr_frag, mfma_tiles.h): lane (h, g & 1, q4, p4) supplies row 16u + 8h + q4 (+ 4 for the high half), elements
         // 16 (g & 1) + 4 p4 .. + 3 of the 32-wide tile; f of that row = q4 << 2 | (2h + e) & 3, whatever u.  o-blocks ob and
         // ob + 4 are 256 bytes apart in a row (f touches the low four chunk bits only).
         int ztr[4][2], xtr[2];
@@ -253,15 +235,6 @@ __global__ __launch_bounds__(512, 1) void bwd256_kernel(B256Args a) {
             for (int ob = 0; ob < 4; ++ob) ztr[ob][e] = row * ZROW + 16 * ((4 * ob + sub) ^ fsw(row)) + 8 * (p4 & 1);
             xtr[e] = ZS + row * XROW + 16 * ((4 * ib + sub) ^ fsw(row)) + 8 * (p4 & 1);
         }
-        typedef s16x4 __attribute__((address_space(3))) lds_s16x4;
-        auto tr_frag = [&](const unsigned char* base, int lo_off, int hi_off) __attribute__((always_inline)) {
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + lo_off));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + hi_off));
-            union { struct { s16x4 a, b; } s; bf16x8 v; } o;
-            o.s.a = lo;
-            o.s.b = hi;
-            return o.v;
-        };
         f32x16 accw[NOB];
 #pragma unroll
         for (int ob = 0; ob < NOB; ++ob)
@@ -330,8 +303,6 @@ __global__ __launch_bounds__(512, 1) void bwd256_kernel(B256Args a) {
         }
     }
 }
-
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 template <int WD>
 int b256_launch(const B256Args& a0, long long M, hipStream_t st) {

@@ -10,10 +10,10 @@
 // sees dh_L and h_{L-1} .. h_{L-n} once each on the way in and dh_{L-n} once on the way out (201 MB for four layers instead of
 // 552 MB), and eight launches become two.  The weight-gradient tiles (n x 64 x 64 fp32) live in the accumulator registers across
 // all tiles of the (persistent) workgroup and leave as PARTIAL tiles, one set per workgroup, that a second small kernel sums into
-// the gradients -- atomics from 512 workgroups on the same 4096 addresses would serialise (gemm_bf16.hip has the numbers).
+// the gradients -- atomics from 512 workgroups on the same 4096 addresses would serialise (mfma_tiles.h, epi_atomic, has the numbers).
 //
 // One LDS image layout serves every use of a tile ([row m][64 columns] bf16, 128-byte rows, 16-byte chunks XOR-swizzled by the
-// row as in gemm_bf16.hip): read with the transposing ds_read_b64_tr_b16 it is the k-slow operand of dW (k = m); read with
+// row: ks_sw<64>, mfma_tiles.h): read with the transposing ds_read_b64_tr_b16 it is the k-slow operand of dW (k = m); read with
 // ds_read_b128 along a row it is the k-fast operand of dX (k = the 64 columns); and lane l of the dX accumulator tile holds
 // column m = its own image row, so the masked result is written back with plain 8-byte stores.  Same arithmetic as the
 // per-layer kernels: bf16 operands, fp32 accumulation, dh rounded to bf16 between layers, db summed from the rounded values.
@@ -22,13 +22,9 @@
 #include <stdlib.h>
 
 #include "moda_hip.h"
-#include "moda_dev.h"
+#include "mfma_tiles.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int W = 64;                      // layer width
 constexpr int RT = 128;                    // rows of a tile
@@ -52,13 +48,6 @@ struct ChainArgs {
     int in_cols, h_cols[MAXL], w_rows[MAXL], w_cols[MAXL], w_ld[MAXL];
 };
 
-DEVINL int sw(int row) { return ((row >> 1) & 1) << 2; }
-DEVINL unsigned pk2(float lo, float hi) {
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-    const f32x2_ t = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2_));
-}
 
 template <int NL>         // layers chained: 4 (the hidden layers 4, 3, 2, 1) or 2 (the heads: rgb -> dir_encoding -> layer D-1); even
 __global__ __launch_bounds__(256, 2) void chain64_kernel(ChainArgs a) {
@@ -70,23 +59,11 @@ __global__ __launch_bounds__(256, 2) void chain64_kernel(ChainArgs a) {
     float* red = (float*)(lds + 2 * IMG + NL * WIMG);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h = lane >> 5, g = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
+    const int h = lane >> 5;
     const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;       // dW: 32 x 32 block of (o, i) per wave
     const int wc2 = (wave & 1) * 64;                             // dX: (i block wr) x (m block wc2 .. + 64)
 
-    // transposing-read bases (gemm_bf16.hip): lane 4q+p of 16-lane group g supplies row 8h + q (+ 16u, + 4), elements
-    // 16 (g & 1) + 4p .. + 3 of the 32-wide block that starts at column `cb`
-    auto tr_base = [&](int cb) { const int ch = cb / 8 + 2 * (g & 1) + (p4 >> 1); return (8 * h + q4) * RB + 16 * (ch ^ sw(q4)) + 8 * (p4 & 1); };
-    const int xb_o = tr_base(wr), yb_i = tr_base(wc);            // dW: X = dh (r = o block), Y = h (c = i block); dX: X = W (r = i block wr)
-    typedef s16x4 __attribute__((address_space(3))) lds_s16x4;
-    auto tr_frag = [&](const unsigned char* base, int off, int u) __attribute__((always_inline)) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off + (16 * u) * RB));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off + (16 * u + 4) * RB));
-        union { struct { s16x4 a, b; } s; bf16x8 v; } o;
-        o.s.a = lo;
-        o.s.b = hi;
-        return o.v;
-    };
+    const int xb_o = tr_base<W>(lane, wr), yb_i = tr_base<W>(lane, wc);      // dW: X = dh (r = o block), Y = h (c = i block); dX: X = W (r = i block wr)
 
     // staging map of a 128 x 64 tile: thread -> 16-byte chunk (tid & 7) of rows (tid >> 3) + 32 e
     const int sch = tid & 7, srow = tid >> 3;
@@ -103,7 +80,7 @@ __global__ __launch_bounds__(256, 2) void chain64_kernel(ChainArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int row = srow + 32 * e;
-            *(uint4*)(img + row * RB + 16 * (sch ^ sw(row))) = src[e];
+            *(uint4*)(img + row * RB + 16 * (sch ^ ks_sw<W>(row))) = src[e];
         }
     };
     // the weights: NL x 8 KB, staged once (a per-step register prefetch of them made every step wait for ALL loads in flight:
@@ -115,7 +92,7 @@ __global__ __launch_bounds__(256, 2) void chain64_kernel(ChainArgs a) {
             const int row = srow + 32 * e;
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
             if (row < a.w_rows[l] && 8 * sch < a.w_cols[l]) v = *(const uint4*)(a.wb[l] + (long long)row * a.w_ld[l] + 8 * sch);
-            *(uint4*)(Ws + l * WIMG + row * RB + 16 * (sch ^ sw(row))) = v;
+            *(uint4*)(Ws + l * WIMG + row * RB + 16 * (sch ^ ks_sw<W>(row))) = v;
         }
 
     f32x16 dw[NL];
@@ -156,8 +133,8 @@ __global__ __launch_bounds__(256, 2) void chain64_kernel(ChainArgs a) {
 #pragma unroll 8
                 for (int rr = 0; rr < 32; ++rr) {
                     const int row = 32 * rg + rr;
-                    const unsigned short v = *(const unsigned short*)(Zs + row * RB + 16 * ((col >> 3) ^ sw(row)) + 2 * (col & 7));
-                    s += __builtin_bit_cast(float, (unsigned)v << 16);
+                    const unsigned short v = *(const unsigned short*)(Zs + row * RB + 16 * ((col >> 3) ^ ks_sw<W>(row)) + 2 * (col & 7));
+                    s += bflo(v);
                 }
                 dbs[l] += s;
             }
@@ -166,12 +143,12 @@ __global__ __launch_bounds__(256, 2) void chain64_kernel(ChainArgs a) {
                 constexpr int AH = 2;
                 bf16x8 xq[AH], yq[AH];
 #pragma unroll
-                for (int u = 0; u < AH; ++u) { xq[u] = tr_frag(Zs, xb_o, u); yq[u] = tr_frag(Hs, yb_i, u); }
+                for (int u = 0; u < AH; ++u) { xq[u] = tr_frag(Zs, xb_o, RB, u); yq[u] = tr_frag(Hs, yb_i, RB, u); }
 #pragma unroll
                 for (int u = 0; u < RT / 16; ++u) {
                     __builtin_amdgcn_sched_barrier(0);
                     dw[l] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xq[u % AH], yq[u % AH], dw[l], 0, 0, 0);
-                    if (u + AH < RT / 16) { xq[u % AH] = tr_frag(Zs, xb_o, u + AH); yq[u % AH] = tr_frag(Hs, yb_i, u + AH); }
+                    if (u + AH < RT / 16) { xq[u % AH] = tr_frag(Zs, xb_o, RB, u + AH); yq[u % AH] = tr_frag(Hs, yb_i, RB, u + AH); }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -183,11 +160,11 @@ __global__ __launch_bounds__(256, 2) void chain64_kernel(ChainArgs a) {
                 for (int r = 0; r < 16; ++r) dx[j][r] = 0.f;
 #pragma unroll
             for (int u = 0; u < W / 16; ++u) {
-                const bf16x8 xa = tr_frag(Ws + l * WIMG, xb_o, u);   // (the i block of the dX product is the same wr as the o block of dW)
+                const bf16x8 xa = tr_frag(Ws + l * WIMG, xb_o, RB, u);   // (the i block of the dX product is the same wr as the o block of dW)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int row = wc2 + 32 * j + (lane & 31);
-                    const bf16x8 yv = *(const bf16x8*)(Zs + row * RB + 16 * ((2 * u + h) ^ sw(row)));
+                    const bf16x8 yv = *(const bf16x8*)(Zs + row * RB + 16 * ((2 * u + h) ^ ks_sw<W>(row)));
                     dx[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa, yv, dx[j], 0, 0, 0);
                 }
             }
@@ -198,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void chain64_kernel(ChainArgs a) {
                 const int row = wc2 + 32 * j + (lane & 31);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int off = row * RB + 16 * (((wr >> 3) + q) ^ sw(row)) + 8 * h;
+                    const int off = row * RB + 16 * (((wr >> 3) + q) ^ ks_sw<W>(row)) + 8 * h;
                     const uint2 m = *(const uint2*)(Hs + off);
                     // bf16 > 0  <=>  its 16 bits, as a signed integer, > 0
                     const float v0 = ((short)(m.x & 0xffffu) > 0) ? dx[j][4 * q] : 0.f, v1 = ((int)m.x > 0xffff) ? dx[j][4 * q + 1] : 0.f;
@@ -214,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void chain64_kernel(ChainArgs a) {
         for (int e = 0; e < 4; ++e) {
             const int row = srow + 32 * e;
             const long long r = r0 + row;
-            if (r < a.M) *(uint4*)(a.dh_out + r * a.ld_out + 8 * sch) = *(const uint4*)(Zs + row * RB + 16 * (sch ^ sw(row)));
+            if (r < a.M) *(uint4*)(a.dh_out + r * a.ld_out + 8 * sch) = *(const uint4*)(Zs + row * RB + 16 * (sch ^ ks_sw<W>(row)));
         }
     }
     // partial tiles: C/D map lane l register r -> row (o) (r&3) + 8(r>>2) + 4(l>>5), column (i) l & 31
@@ -262,19 +239,9 @@ __global__ __launch_bounds__(256, 2) void pe_ends64_kernel(PeEndsArgs a) {
     float* dpe = (float*)lds;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h = lane >> 5, g = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
+    const int h = lane >> 5;
     const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32, wc2 = (wave & 1) * 64;
-    auto tr_base = [&](int cb) { const int ch = cb / 8 + 2 * (g & 1) + (p4 >> 1); return (8 * h + q4) * RB + 16 * (ch ^ sw(q4)) + 8 * (p4 & 1); };
-    const int xb_o = tr_base(wr), yb_i = tr_base(wc);
-    typedef s16x4 __attribute__((address_space(3))) lds_s16x4;
-    auto tr_frag = [&](const unsigned char* base, int off, int u) __attribute__((always_inline)) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off + (16 * u) * RB));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off + (16 * u + 4) * RB));
-        union { struct { s16x4 a, b; } s; bf16x8 v; } o;
-        o.s.a = lo;
-        o.s.b = hi;
-        return o.v;
-    };
+    const int xb_o = tr_base<W>(lane, wr), yb_i = tr_base<W>(lane, wc);
     const int sch = tid & 7, srow = tid >> 3;
     uint4 za[4], zb[4], pr[4];
     auto fetch_tile = [&](const unsigned short* src, long long ld, long long r0, uint4 (&dst)[4]) __attribute__((always_inline)) {
@@ -289,14 +256,14 @@ __global__ __launch_bounds__(256, 2) void pe_ends64_kernel(PeEndsArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int row = srow + 32 * e;
-            *(uint4*)(img + row * RB + 16 * (sch ^ sw(row))) = src[e];
+            *(uint4*)(img + row * RB + 16 * (sch ^ ks_sw<W>(row))) = src[e];
         }
     };
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
         const int row = srow + 32 * e;
-        *(uint4*)(Ws + row * RB + 16 * (sch ^ sw(row))) = *(const uint4*)(a.wa + row * W + 8 * sch);
-        *(uint4*)(Ws + WIMG + row * RB + 16 * (sch ^ sw(row))) = *(const uint4*)(a.wb + row * W + 8 * sch);
+        *(uint4*)(Ws + row * RB + 16 * (sch ^ ks_sw<W>(row))) = *(const uint4*)(a.wa + row * W + 8 * sch);
+        *(uint4*)(Ws + WIMG + row * RB + 16 * (sch ^ ks_sw<W>(row))) = *(const uint4*)(a.wb + row * W + 8 * sch);
     }
     f32x16 dwa, dwb;
 #pragma unroll
@@ -328,16 +295,16 @@ __global__ __launch_bounds__(256, 2) void pe_ends64_kernel(PeEndsArgs a) {
 #pragma unroll 8
             for (int rr = 0; rr < 32; ++rr) {
                 const int row = 32 * rg + rr;
-                const unsigned short v = *(const unsigned short*)(Zb + row * RB + 16 * ((col >> 3) ^ sw(row)) + 2 * (col & 7));
-                s += __builtin_bit_cast(float, (unsigned)v << 16);
+                const unsigned short v = *(const unsigned short*)(Zb + row * RB + 16 * ((col >> 3) ^ ks_sw<W>(row)) + 2 * (col & 7));
+                s += bflo(v);
             }
             dbs += s;
         }
 #pragma unroll
         for (int u = 0; u < RT / 16; ++u) {
-            const bf16x8 yv = tr_frag(Ps, yb_i, u);
-            dwa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(Za, xb_o, u), yv, dwa, 0, 0, 0);
-            dwb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(Zb, xb_o, u), yv, dwb, 0, 0, 0);
+            const bf16x8 yv = tr_frag(Ps, yb_i, RB, u);
+            dwa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(Za, xb_o, RB, u), yv, dwa, 0, 0, 0);
+            dwb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(Zb, xb_o, RB, u), yv, dwb, 0, 0, 0);
         }
         // d_pe: T[pe][m] = sum_o Wa[o][pe] dh_a[m][o] + Wb[o][pe] dh_b[m][o]; wave: pe block wr, m blocks wc2, wc2 + 32
         f32x16 dx[2];
@@ -347,11 +314,11 @@ __global__ __launch_bounds__(256, 2) void pe_ends64_kernel(PeEndsArgs a) {
             for (int r = 0; r < 16; ++r) dx[j][r] = 0.f;
 #pragma unroll
         for (int u = 0; u < W / 16; ++u) {
-            const bf16x8 xa = tr_frag(Ws, xb_o, u), xb = tr_frag(Ws + WIMG, xb_o, u);
+            const bf16x8 xa = tr_frag(Ws, xb_o, RB, u), xb = tr_frag(Ws + WIMG, xb_o, RB, u);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int row = wc2 + 32 * j + (lane & 31);
-                const int off = row * RB + 16 * ((2 * u + h) ^ sw(row));
+                const int off = row * RB + 16 * ((2 * u + h) ^ ks_sw<W>(row));
                 dx[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa, *(const bf16x8*)(Za + off), dx[j], 0, 0, 0);
                 dx[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xb, *(const bf16x8*)(Zb + off), dx[j], 0, 0, 0);
             }

@@ -26,14 +26,9 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
-#include "moda_dev.h"
+#include "mfma_tiles.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KT = 64;                    // k per tile: four 32x32x16 steps
 constexpr int KF_STRIDE = KT * 2 + 16;    // bytes per row of a k-fast image (144: sixteen consecutive rows cover all 64 banks)
@@ -53,26 +48,7 @@ struct G3Args {
     unsigned gr, gc;                      // tiles along r / c
 };
 
-// chunk swizzle of a [k][T] bf16 image (rows of 2T bytes, 16-byte chunks): the four rows one transposing read takes
-// (4n .. 4n+3, 64 bytes each per 32-lane half) land in four different 64-byte bank groups
-template <int T>
-DEVINL int ks_sw(int row) { return T == 128 ? ((row & 3) << 2) : (((row >> 1) & 1) << 2); }
-
-DEVINL unsigned pk2(float lo, float hi) {
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-    const f32x2_ t = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2_));
-}
-DEVINL uint4 pack8(const float4& a, const float4& b) { return make_uint4(pk2(a.x, a.y), pk2(a.z, a.w), pk2(b.x, b.y), pk2(b.z, b.w)); }
-DEVINL float bflo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-DEVINL float bfhi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-
-// NG (dW form): wave groups per workgroup.  Each group of 4 waves is a complete 2 x 2 tile engine with its own LDS stage and
-// its own k-tiles; the groups' accumulators are summed through LDS before ONE set of atomics leaves the workgroup.  The
-// atomics of all workgroups land on the same R x C addresses and serialise there (~37 ns per workgroup whatever the tile:
-// 19 of the 23 us of a 64 x 64 product at 512 workgroups), while the stream needs many k-tiles in flight: NG groups give
-// the memory parallelism of NG workgroups at the atomic cost of one.
+// NG (dW form): wave groups per workgroup, each a complete 2 x 2 tile engine on its own k-tiles (mfma_tiles.h, epi_atomic)
 template <int TR, int TC, bool X32, bool YKF, bool Y32, int EPI, int NG = 1>
 __global__ __launch_bounds__(256 * NG, NG == 1 ? 2 : 1) void gemm3_kernel(G3Args a) {
     static_assert(!(YKF && Y32), "the k-fast operand is bf16");
@@ -93,49 +69,16 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? 2 : 1) void gemm3_kernel(G3Args
     unsigned char* Ys = Xs + XS_BYTES;
 
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-    const int h = lane >> 5, g = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
+    const int h = lane >> 5;
     const int wr = (wave >> 1) * WR, wc = (wave & 1) * WC;
-    // tiles that share their Y rows (the long operand of the dX form) get dispatch ids 8 apart: one XCD, one L2
-    // (workgroups are dealt round-robin over the 8 XCDs, each with its own L2: what one XCD has fetched, another fetches again)
-    const unsigned lid = blockIdx.x;
-    unsigned tr_idx, tc_idx, slice = 0;
-    if (EPI == EPI_ATOMIC) {
-        // the tiles of one k slice read the same rows of dZ and X: dispatch ids 8 apart, so that one XCD's L2 serves the
-        // second reader of every chunk (measured without: every operand byte crosses the fabric once per tile column / row)
-        const unsigned nt = a.gr * a.gc;
-        unsigned t = lid % nt;
-        slice = lid / nt;
-        if ((a.splits & 7) == 0) {
-            t = (lid >> 3) % nt;
-            slice = (lid / (8 * nt)) * 8 + (lid & 7);
-        }
-        tr_idx = t % a.gr;
-        tc_idx = t / a.gr;
-    } else {
-        tr_idx = lid % a.gr;
-        tc_idx = lid / a.gr;
-        if (a.gr > 1 && (a.gc & 7) == 0) {
-            const unsigned span = 8 * a.gr, r = lid % span;
-            tr_idx = r >> 3;
-            tc_idx = (lid / span) * 8 + (r & 7);
-        }
-    }
+    unsigned tr_idx, tc_idx, slice;
+    place_tile<EPI == EPI_ATOMIC>(blockIdx.x, a.gr, a.gc, a.splits, tr_idx, tc_idx, slice);
     const long long r0 = (long long)tr_idx * TR, c0 = (long long)tc_idx * TC;
-    // split over k: engine e of E = splits x NG (slice s, group g: e = s NG + g) takes the k-tiles e, e + E, e + 2E, ...:
-    // engines that run at the same time read neighbouring 64-row pieces of the operands (measured the same as one
-    // contiguous range per engine; kept because it makes the ranges independent of K)
-    const int kstep = KT * a.splits * NG;
-    const int kbeg = ((int)slice * NG + grp) * KT;
-    const int kend = a.K;
-    const int nit = (kend - (int)slice * NG * KT + kstep - 1) / kstep;    // trips of group 0, the longest: every group runs as many
+    const KSched ks = k_schedule<KT, NG>(a.K, a.splits, (int)slice, grp);
+    const int kstep = ks.kstep, kbeg = ks.kbeg, nit = ks.nit, kend = a.K;
 
     f32x16 acc[NI][NJ];
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    clear_acc(acc);
 
     // ---- staging: thread -> (row, 16-byte chunk) of each image, the same chunk column in every pass --------------------
     constexpr int XCPR = TR / 8, XRPP = 256 / XCPR, XNP = KT / XRPP;
@@ -220,33 +163,12 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? 2 : 1) void gemm3_kernel(G3Args
         }
     };
 
-    // ---- per-lane bases of the fragment reads.  Transposing read of a [k][T] image, 16-lane group gq = g & 1 of lane half
-    //      h: lane 4q+p supplies row (16u + 8h + 4e) + q, elements 16 gq + 4p .. +3 of the 32-wide tile; it receives, for
-    //      its own column (lane & 31), the k = 8h + 4e + (0..3) of k-step u -- elements 4e .. 4e+3 of the MFMA operand.
+    // ---- per-lane bases of the fragment reads (mfma_tiles.h) ----
     int xb[NI], yb[NJ];
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int ch = (wr + 32 * i) / 8 + 2 * (g & 1) + (p4 >> 1);
-        xb[i] = (8 * h + q4) * RBX + 16 * (ch ^ ks_sw<TR>(q4)) + 8 * (p4 & 1);
-    }
+    for (int i = 0; i < NI; ++i) xb[i] = tr_base<TR>(lane, wr + 32 * i);
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        if (YKF) {
-            yb[j] = (wc + 32 * j + (lane & 31)) * KF_STRIDE + 16 * h;
-        } else {
-            const int ch = (wc + 32 * j) / 8 + 2 * (g & 1) + (p4 >> 1);
-            yb[j] = (8 * h + q4) * RBY + 16 * (ch ^ ks_sw<TC>(q4)) + 8 * (p4 & 1);
-        }
-    }
-    typedef s16x4 __attribute__((address_space(3))) lds_s16x4;
-    auto tr_frag = [&](const unsigned char* base, int off, int rb, int u) __attribute__((always_inline)) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off + (16 * u) * rb));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off + (16 * u + 4) * rb));
-        union { struct { s16x4 a, b; } s; bf16x8 v; } o;
-        o.s.a = lo;
-        o.s.b = hi;
-        return o.v;
-    };
+    for (int j = 0; j < NJ; ++j) yb[j] = YKF ? kf_base(lane, wc + 32 * j, KF_STRIDE) : tr_base<TC>(lane, wc + 32 * j);
 
     if (nit > 0) fetch(kbeg);
     for (int it = 0; it < nit; ++it) {      // (a k-tile past the end loads zeros)
@@ -272,67 +194,8 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? 2 : 1) void gemm3_kernel(G3Args
         __syncthreads();
     }
 
-    // C/D map: lane l register r -> T row (r&3) + 8(r>>2) + 4(l>>5), T column l & 31
     if (EPI == EPI_ATOMIC) {
-        if (NG > 1) {       // sum the groups' partial tiles into group 0 (lane-linear fp32 images in the now idle stage LDS)
-            float* part = (float*)lds;
-            if (grp > 0) {
-#pragma unroll
-                for (int i = 0; i < NI; ++i)
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) part[(((grp - 1) * NREG) + (i * NJ + j) * 16 + r) * 256 + tid] = acc[i][j][r];
-            }
-            __syncthreads();
-            if (grp == 0) {
-#pragma unroll
-                for (int g2 = 1; g2 < NG; ++g2)
-#pragma unroll
-                    for (int i = 0; i < NI; ++i)
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) acc[i][j][r] += part[(((g2 - 1) * NREG) + (i * NJ + j) * 16 + r) * 256 + tid];
-            }
-            if (do_xsum) {
-                __syncthreads();
-                float* red = (float*)lds;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) red[((grp * 256) + xrow * XCPR + xch) * 8 + e] = xsum8[e];
-                __syncthreads();
-                if (grp == 0 && tid < TR) {
-                    float sm = 0.f;
-                    for (int rw = 0; rw < NG * XRPP; ++rw) sm += red[(rw * XCPR + (tid >> 3)) * 8 + (tid & 7)];
-                    if (r0 + tid < a.R) atomicAdd(a.xsum + r0 + tid, sm);
-                }
-            }
-            if (grp != 0) return;
-        }
-        float* C = (float*)a.C;
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const long long c = c0 + wc + 32 * j + (lane & 31);
-                if (c >= a.Cn) continue;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const long long rr = r0 + wr + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (rr < a.R) atomicAdd(C + rr * a.ldc + c, acc[i][j][r]);
-                }
-            }
-        if (NG == 1 && do_xsum) {      // threads with the same chunk column hold partial sums of the same eight r
-            float* red = (float*)lds;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) red[(xrow * XCPR + xch) * 8 + e] = xsum8[e];
-            __syncthreads();
-            if (tid < TR) {
-                float s = 0.f;
-                for (int rw = 0; rw < XRPP; ++rw) s += red[(rw * XCPR + (tid >> 3)) * 8 + (tid & 7)];
-                if (r0 + tid < a.R) atomicAdd(a.xsum + r0 + tid, s);
-            }
-        }
+        epi_atomic<TR, TC, NG, XCPR, XRPP>(acc, xsum8, lds, grp, tid, (float*)a.C, a.ldc, do_xsum ? a.xsum : nullptr, r0, c0, a.R, a.Cn);
         return;
     }
     // ---- transposed store: the wave writes one 32-column (c) slab of its tile at a time into its LDS buffer as
@@ -382,13 +245,7 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? 2 : 1) void gemm3_kernel(G3Args
                     v = make_uint4(keepb(v.x, bm), keepb(v.y, bm >> 2), keepb(v.z, bm >> 4), keepb(v.w, bm >> 6));
                 } else if (a.mask != nullptr) {
                     const uint4 m = *(const uint4*)(a.mask + c * a.ldm + rr);
-                    // bf16 > 0  <=>  its 16 bits, as a signed integer, > 0
-                    auto keep = [](unsigned vw, unsigned mw) {
-                        const unsigned lo = ((short)(mw & 0xffffu) > 0) ? 0x0000ffffu : 0u;
-                        const unsigned hi = ((int)mw > 0xffff) ? 0xffff0000u : 0u;      // high half positive and nonzero
-                        return vw & (lo | hi);
-                    };
-                    v = make_uint4(keep(v.x, m.x), keep(v.y, m.y), keep(v.z, m.z), keep(v.w, m.w));
+                    v = make_uint4(keep_pos(v.x, m.x), keep_pos(v.y, m.y), keep_pos(v.z, m.z), keep_pos(v.w, m.w));
                 }
                 *(uint4*)cp = v;
             }
@@ -402,8 +259,6 @@ int g3_launch(const G3Args& a, unsigned splits, hipStream_t st) {
     hipLaunchKernelGGL((gemm3_kernel<TR, TC, X32, YKF, Y32, EPI, NG>), dim3(a.gr * a.gc * splits), dim3(256 * NG), 0, st, a);
     return (int)hipGetLastError();
 }
-
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 }   // namespace
 
@@ -434,21 +289,11 @@ bool moda_g3_try(const moda_gemm_desc* d, void* stream, int* rc) {
             if (!b_bf || Cn % 8 || d->ld_bits < Cn / 8) return false;
             a.bits = (unsigned char*)d->mask_bits; a.ldb = d->ld_bits;
         }
-        const bool big = R > 64 || Cn > 64;                            // 128 x 128 tiles, or 64 x 64 for the 64-wide nets
-        const int T = big ? 128 : 64;
-        a.gr = (unsigned)((R + T - 1) / T); a.gc = (unsigned)((Cn + T - 1) / T);
-        // split over k: one workgroup per CU (NG wave groups each), every engine with at least two k-tiles
         static const long long target_env = [] { const char* e = getenv("MODA_GEMM3_BLOCKS"); return e ? atoll(e) : 0LL; }();
-        const long long target = target_env > 0 ? target_env : (big ? 256 : 128);    // measured best (64 .. 512 swept)
-        const int ng = big ? 2 : 4;
-        const long long nkt = (K + KT - 1) / KT;
-        long long splits = target / ((long long)a.gr * a.gc);
-        if (splits > nkt / (2 * ng)) splits = nkt / (2 * ng);
-        if (splits < 1) splits = 1;
-        if (splits >= 8) splits &= ~7LL;              // whole groups of 8 slices: the XCD placement in the kernel
-        const unsigned zs = (unsigned)splits;
-        a.splits = (int)splits;
-        if (big) *rc = b_bf ? g3_launch<128, 128, false, false, false, EPI_ATOMIC, 2>(a, zs, st)
+        const DwPlan pl = plan_dw_splits(R, Cn, K, KT, target_env);
+        const unsigned zs = pl.splits;
+        a.gr = pl.gr; a.gc = pl.gc; a.splits = (int)zs;
+        if (pl.big) *rc = b_bf ? g3_launch<128, 128, false, false, false, EPI_ATOMIC, 2>(a, zs, st)
                             : g3_launch<128, 128, false, false, true, EPI_ATOMIC, 2>(a, zs, st);
         else *rc = b_bf ? g3_launch<64, 64, false, false, false, EPI_ATOMIC, 4>(a, zs, st)
                         : g3_launch<64, 64, false, false, true, EPI_ATOMIC, 4>(a, zs, st);

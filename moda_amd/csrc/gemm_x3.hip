@@ -25,13 +25,9 @@
 #include <type_traits>
 
 #include "moda_hip.h"
-#include "moda_dev.h"
+#include "mfma_tiles.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KT = 32;                    // k per tile: two 32x32x16 steps
 constexpr int PF = 1;                     // k-tiles of global loads in flight per engine
@@ -55,26 +51,13 @@ struct X3Args {
     unsigned gr, gc;                      // tiles along r / c
 };
 
-// chunk swizzle of a [k][T] bf16 image (rows of 2T bytes, 16-byte chunks): the four rows one transposing read takes
-// (4n .. 4n+3, 64 bytes each per 32-lane half) land in four different 64-byte bank groups
-template <int T>
-DEVINL int ks_sw(int row) { return T == 128 ? ((row & 3) << 2) : (((row >> 1) & 1) << 2); }
-
-DEVINL unsigned pk2(float lo, float hi) {
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-    const f32x2_ t = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2_));
-}
-DEVINL float bflo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-DEVINL float bfhi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
 // eight fp32 values -> NS bf16 images: the rounding of the value, then of what each rounding left behind (the differences are
 // exact in fp32: a bf16 keeps the top 8 significand bits of its argument)
 template <int NS>
 DEVINL void split8(float4 a, float4 b, uint4 (&o)[NS]) {
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        const uint4 w = make_uint4(pk2(a.x, a.y), pk2(a.z, a.w), pk2(b.x, b.y), pk2(b.z, b.w));
+        const uint4 w = pack8(a, b);
         o[s] = w;
         if (s + 1 < NS) {
             a.x -= bflo(w.x); a.y -= bfhi(w.x); a.z -= bflo(w.y); a.w -= bfhi(w.y);
@@ -84,7 +67,7 @@ DEVINL void split8(float4 a, float4 b, uint4 (&o)[NS]) {
 }
 
 // NG (dW form): wave groups per workgroup, each a complete 2 x 2 tile engine with its own LDS stage and its own k-tiles; the
-// groups' accumulators are summed through LDS before ONE set of atomics leaves the workgroup (gemm_bf16.hip has the numbers).
+// groups' accumulators are summed through LDS before ONE set of atomics leaves the workgroup (mfma_tiles.h, epi_atomic, has the numbers).
 // (Round 4 tried NG = 2 on the row forms as a PING-PONG: two wave groups on adjacent c tiles, one barrier apart, so that on every
 // SIMD one wave stages while the other multiplies.  Correct, and 8-30 % SLOWER than two independent workgroups per CU (256-wide
 // bf16x6 forward 326 vs 302 us, masked dX 401 vs 306 us on random operands): the workgroup-wide barrier ties each group to the
@@ -111,45 +94,16 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? (NS == 2 ? 3 : 2) : 1) void gem
     unsigned char* Ys = Xs + XS_BYTES;
 
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-    const int h = lane >> 5, g = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
+    const int h = lane >> 5;
     const int wr = (wave >> 1) * WR, wc = (wave & 1) * WC;
-    // tiles that read the same rows of a long operand get dispatch ids 8 apart: one XCD, one L2 (workgroups are dealt
-    // round-robin over the 8 XCDs, each with its own L2: what one XCD has fetched, another fetches again)
-    const unsigned lid = blockIdx.x;
-    unsigned tr_idx, tc_idx, slice = 0;
-    if (EPI == EPI_ATOMIC) {
-        const unsigned nt = a.gr * a.gc;
-        unsigned t = lid % nt;
-        slice = lid / nt;
-        if ((a.splits & 7) == 0) {
-            t = (lid >> 3) % nt;
-            slice = (lid / (8 * nt)) * 8 + (lid & 7);
-        }
-        tr_idx = t % a.gr;
-        tc_idx = t / a.gr;
-    } else {
-        tr_idx = lid % a.gr;
-        tc_idx = lid / a.gr;
-        if (a.gr > 1 && (a.gc & 7) == 0) {
-            const unsigned span = 8 * a.gr, r = lid % span;
-            tr_idx = r >> 3;
-            tc_idx = (lid / span) * 8 + (r & 7);
-        }
-    }
+    unsigned tr_idx, tc_idx, slice;
+    place_tile<EPI == EPI_ATOMIC>(blockIdx.x, a.gr, a.gc, a.splits, tr_idx, tc_idx, slice);
     const long long r0 = (long long)tr_idx * TR, c0 = (long long)tc_idx * TC;
-    // split over k: engine e of E = splits x NG (slice s, group g: e = s NG + g) takes the k-tiles e, e + E, e + 2E, ...
-    const int kstep = KT * a.splits * NG;
-    const int kbeg = ((int)slice * NG + grp) * KT;
-    const int kend = a.K;
-    const int nit = (kend - (int)slice * NG * KT + kstep - 1) / kstep;    // trips of group 0, the longest: every group runs as many
+    const KSched ks = k_schedule<KT, NG>(a.K, a.splits, (int)slice, grp);
+    const int kstep = ks.kstep, kbeg = ks.kbeg, nit = ks.nit, kend = a.K;
 
     f32x16 acc[NI][NJ];
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    clear_acc(acc);
 
     // ---- staging: a thread takes eight consecutive fp32 (two 16-byte loads) = one 16-byte chunk of each bf16 image ------------
     //      k-slow: (row k, chunk of eight tile columns);  k-fast: (tile row, chunk of eight k: KT / 8 = 4 chunks per row)
@@ -243,38 +197,12 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? (NS == 2 ? 3 : 2) : 1) void gem
         }
     };
 
-    // ---- per-lane bases of the fragment reads.  Transposing read of a [k][T] image, 16-lane group gq = g & 1 of lane half
-    //      h: lane 4q+p supplies row (16u + 8h + 4e) + q, elements 16 gq + 4p .. +3 of the 32-wide tile; it receives, for
-    //      its own column (lane & 31), the k = 8h + 4e + (0..3) of k-step u -- elements 4e .. 4e+3 of the MFMA operand.
-    //      k-fast image: the lane reads its own row's eight k = 16u + 8h .. +7 with one 16-byte read.
+    // ---- per-lane bases of the fragment reads (mfma_tiles.h) ----
     int xb[NI], yb[NJ];
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        if (XKF) {
-            xb[i] = (wr + 32 * i + (lane & 31)) * KF_STRIDE + 16 * h;
-        } else {
-            const int ch = (wr + 32 * i) / 8 + 2 * (g & 1) + (p4 >> 1);
-            xb[i] = (8 * h + q4) * RBX + 16 * (ch ^ ks_sw<TR>(q4)) + 8 * (p4 & 1);
-        }
-    }
+    for (int i = 0; i < NI; ++i) xb[i] = XKF ? kf_base(lane, wr + 32 * i, KF_STRIDE) : tr_base<TR>(lane, wr + 32 * i);
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        if (YKF) {
-            yb[j] = (wc + 32 * j + (lane & 31)) * KF_STRIDE + 16 * h;
-        } else {
-            const int ch = (wc + 32 * j) / 8 + 2 * (g & 1) + (p4 >> 1);
-            yb[j] = (8 * h + q4) * RBY + 16 * (ch ^ ks_sw<TC>(q4)) + 8 * (p4 & 1);
-        }
-    }
-    typedef s16x4 __attribute__((address_space(3))) lds_s16x4;
-    auto tr_frag = [&](const unsigned char* base, int off, int rb, int u) __attribute__((always_inline)) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off + (16 * u) * rb));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off + (16 * u + 4) * rb));
-        union { struct { s16x4 a, b; } s; bf16x8 v; } o;
-        o.s.a = lo;
-        o.s.b = hi;
-        return o.v;
-    };
+    for (int j = 0; j < NJ; ++j) yb[j] = YKF ? kf_base(lane, wc + 32 * j, KF_STRIDE) : tr_base<TC>(lane, wc + 32 * j);
 
     auto multiply = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -323,68 +251,11 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? (NS == 2 ? 3 : 2) : 1) void gem
         __syncthreads();
     }
 
-    // C/D map: lane l register r -> T row (r&3) + 8(r>>2) + 4(l>>5), T column l & 31
     if (EPI == EPI_ATOMIC) {
-        if (NG > 1) {       // sum the groups' partial tiles into group 0 (lane-linear fp32 images in the now idle stage LDS)
-            float* part = (float*)lds;
-            if (grp > 0) {
-#pragma unroll
-                for (int i = 0; i < NI; ++i)
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) part[(((grp - 1) * NREG) + (i * NJ + j) * 16 + r) * 256 + tid] = acc[i][j][r];
-            }
-            __syncthreads();
-            if (grp == 0) {
-#pragma unroll
-                for (int g2 = 1; g2 < NG; ++g2)
-#pragma unroll
-                    for (int i = 0; i < NI; ++i)
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) acc[i][j][r] += part[(((g2 - 1) * NREG) + (i * NJ + j) * 16 + r) * 256 + tid];
-            }
-            if (do_xsum) {
-                __syncthreads();
-                float* red = (float*)lds;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) red[((grp * 256) + xrow * XCPR + xch) * 8 + e] = xsum8[e];
-                __syncthreads();
-                if (grp == 0 && tid < TR) {
-                    float sm = 0.f;
-                    for (int rw = 0; rw < NG * XRPP; ++rw) sm += red[(rw * XCPR + (tid >> 3)) * 8 + (tid & 7)];
-                    if (r0 + tid < a.R) atomicAdd(a.xsum + r0 + tid, sm);
-                }
-            }
-            if (grp != 0) return;
-        }
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const long long c = c0 + wc + 32 * j + (lane & 31);
-                if (c >= a.Cn) continue;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const long long rr = r0 + wr + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (rr < a.R) atomicAdd(a.C + rr * a.ldc + c, acc[i][j][r]);
-                }
-            }
-        if (NG == 1 && do_xsum) {      // threads with the same chunk column hold partial sums of the same eight r
-            float* red = (float*)lds;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) red[(xrow * XCPR + xch) * 8 + e] = xsum8[e];
-            __syncthreads();
-            if (tid < TR) {
-                float s = 0.f;
-                for (int rw = 0; rw < XRPP; ++rw) s += red[(rw * XCPR + (tid >> 3)) * 8 + (tid & 7)];
-                if (r0 + tid < a.R) atomicAdd(a.xsum + r0 + tid, s);
-            }
-        }
+        epi_atomic<TR, TC, NG, XCPR, XRPP>(acc, xsum8, lds, grp, tid, a.C, a.ldc, do_xsum ? a.xsum : nullptr, r0, c0, a.R, a.Cn);
         return;
     }
+    // C/D map: lane l register r -> T row (r&3) + 8(r>>2) + 4(l>>5), T column l & 31
     // ---- transposed store: the wave writes one 32-column (c) slab of its tile at a time into its LDS buffer as [c][r] rows,
     //      then every lane takes 16 bytes (four r) of one row: coalesced bias / mask / C reads and C stores -------------------
     unsigned char* tb = lds + wave * (32 * EPI_ROW);
@@ -445,8 +316,6 @@ int x3_launch(const X3Args& a, int ns, unsigned splits, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 }   // namespace
 
 // Route of moda_gemm_f32_ex for MODA_GEMM_BF16X3 / MODA_GEMM_BF16X6 calls (ns = 2 / 3 images per operand): returns true (and the launch status in *rc) when the call is one of the
@@ -472,21 +341,11 @@ bool moda_x3_try(const moda_gemm_desc* d, int ns, void* stream, int* rc) {
         a.R = (int)R; a.Cn = (int)Cn; a.K = (int)K; a.xsum = d->a_sum;
         if (d->mask_bits && d->ld_bits * 8 < Cn) return false;
         a.bits_out = (unsigned char*)d->mask_bits;       // written: the sign map of B (moda_hip.h, moda_gemm_desc.mask_bits)
-        const bool big = R > 64 || Cn > 64;                            // 128 x 128 tiles, or 64 x 64 for the 64-wide nets
-        const int T = big ? 128 : 64;
-        a.gr = (unsigned)((R + T - 1) / T); a.gc = (unsigned)((Cn + T - 1) / T);
-        // split over k: one workgroup per CU (NG wave groups each), every engine with at least two k-tiles
         static const long long target_env = [] { const char* e = getenv("MODA_GEMM_X3_BLOCKS"); return e ? atoll(e) : 0LL; }();
-        const long long target = target_env > 0 ? target_env : (big ? 256 : 128);
-        const int ng = big ? 2 : 4;
-        const long long nkt = (K + KT - 1) / KT;
-        long long splits = target / ((long long)a.gr * a.gc);
-        if (splits > nkt / (2 * ng)) splits = nkt / (2 * ng);
-        if (splits < 1) splits = 1;
-        if (splits >= 8) splits &= ~7LL;              // whole groups of 8 slices: the XCD placement in the kernel
-        a.splits = (int)splits;
-        if (big) *rc = x3_launch<128, 128, false, false, EPI_ATOMIC, 2>(a, ns, (unsigned)splits, st);
-        else *rc = x3_launch<64, 64, false, false, EPI_ATOMIC, 4>(a, ns, (unsigned)splits, st);
+        const DwPlan pl = plan_dw_splits(R, Cn, K, KT, target_env);
+        a.gr = pl.gr; a.gc = pl.gc; a.splits = (int)pl.splits;
+        if (pl.big) *rc = x3_launch<128, 128, false, false, EPI_ATOMIC, 2>(a, ns, pl.splits, st);
+        else *rc = x3_launch<64, 64, false, false, EPI_ATOMIC, 4>(a, ns, pl.splits, st);
         return true;
     }
     if (d->sak == 1) {

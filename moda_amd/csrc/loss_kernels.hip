@@ -11,7 +11,7 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
-#include "moda_dev.h"
+#include "mfma_tiles.h"
 
 namespace {
 
@@ -21,14 +21,9 @@ constexpr int kFdRows = 16;         // rows of the matching matrix per workgroup
 // The matching matrix Kmat / KmatT may be held as bf16 (`bf`: the throughput mode of the training route -- the 78 Sinkhorn
 // sweeps of a step read it 78 times); element i of either form:
 DEVINL float kld(const float* K, long long i, int bf) {
-    return bf ? __builtin_bit_cast(float, (unsigned)((const unsigned short*)K)[i] << 16) : K[i];
+    return bf ? bflo(((const unsigned short*)K)[i]) : K[i];
 }
-DEVINL unsigned short f2bf(float v) {      // round to nearest even
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-    const f32x2_ t = {v, 0.f};
-    return (unsigned short)(__builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2_)) & 0xffffu);
-}
+DEVINL unsigned short f2bf(float v) { return (unsigned short)(pk2(v, 0.f) & 0xffffu); }      // round to nearest even
 constexpr float kSinkEps = 1e-8f;   // loss_utils.py:366,369
 
 DEVINL float wave_sum(float v) { return comp_wave_sum(v); }      // (DPP / lane-swap form, bitwise the shuffle butterfly: moda_dev.h)
@@ -127,10 +122,8 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(const float* __restrict_
         const float4* x4 = (const float4*)x;
         float t0 = 0.f, t1 = 0.f;
         auto dot8 = [](const uint4& a, const float4& b0, const float4& b1) {
-            return __builtin_bit_cast(float, a.x << 16) * b0.x + __builtin_bit_cast(float, a.x & 0xffff0000u) * b0.y +
-                   __builtin_bit_cast(float, a.y << 16) * b0.z + __builtin_bit_cast(float, a.y & 0xffff0000u) * b0.w +
-                   __builtin_bit_cast(float, a.z << 16) * b1.x + __builtin_bit_cast(float, a.z & 0xffff0000u) * b1.y +
-                   __builtin_bit_cast(float, a.w << 16) * b1.z + __builtin_bit_cast(float, a.w & 0xffff0000u) * b1.w;
+            return bflo(a.x) * b0.x + bfhi(a.x) * b0.y + bflo(a.y) * b0.z + bfhi(a.y) * b0.w +
+                   bflo(a.z) * b1.x + bfhi(a.z) * b1.y + bflo(a.w) * b1.z + bfhi(a.w) * b1.w;
         };
         int q = lane;
         for (; q + 64 < C8; q += 128) {
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(const float* __restrict_
             t1 += dot8(a1, x4[2 * q + 128], x4[2 * q + 129]);
         }
         for (; q < C8; q += 64) t0 += dot8(row8[q], x4[2 * q], x4[2 * q + 1]);
-        for (int g = 8 * C8 + lane; g < C; g += 64) t1 += __builtin_bit_cast(float, (unsigned)rowh[g] << 16) * x[g];
+        for (int g = 8 * C8 + lane; g < C; g += 64) t1 += bflo(rowh[g]) * x[g];
         const float sb = wave_sum(t0 + t1);
         if (lane == 0) out[r] = sweep_epilogue(sb, mode, p, c ? c[r] : 0.f);
         return;

@@ -1,5 +1,6 @@
-// Device helpers shared by the kernels of libmoda_hip.so (render_kernels.hip, mlp_fused.hip): quaternion algebra, the
-// DQS point transform, and the layout of the per-set MFMA tables of the fused skin-MLP + warp kernel.
+// Device helpers shared by the kernels of libmoda_hip.so (every .hip file of this directory includes it, the bf16 training
+// kernels through mfma_tiles.h): DEVINL, the internal entry points between the files, sincos_rr, quaternion algebra, the DQS
+// point transform, the compositing core, and the layout of the per-set MFMA tables of the fused skin-MLP + warp kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -6,11 +6,10 @@
 #include <stdlib.h>
 
 #include "moda_hip.h"
-#include "moda_dev.h"
+#include "mfma_tiles.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define DEVINL __device__ __forceinline__
 
 constexpr int BM = 128, BK = 16;
@@ -135,30 +134,22 @@ struct Gemm2Args {
 };
 
 // ---- element access by storage type: `off` counts elements from `base` -------------------------------------------------
-DEVINL float g2_bf2f(unsigned short v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
 DEVINL float g2_ld1(const float* __restrict__ base, long long off, int bf) {
-    return bf ? g2_bf2f(((const unsigned short*)base)[off]) : base[off];
+    return bf ? bflo(((const unsigned short*)base)[off]) : base[off];
 }
 DEVINL float4 g2_ld4(const float* __restrict__ base, long long off, int bf) {     // 4 consecutive elements, vector-aligned
     if (bf) {
         const uint2 u = *(const uint2*)((const unsigned short*)base + off);
-        return make_float4(__builtin_bit_cast(float, u.x << 16), __builtin_bit_cast(float, u.x & 0xffff0000u),
-                           __builtin_bit_cast(float, u.y << 16), __builtin_bit_cast(float, u.y & 0xffff0000u));
+        return make_float4(bflo(u.x), bfhi(u.x), bflo(u.y), bfhi(u.y));
     }
     return *(const float4*)(base + off);
 }
-DEVINL unsigned g2_pack2(float lo, float hi) {       // two floats -> two bf16 (round to nearest even), lo in the low half
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-    const f32x2_ t = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2_));
-}
 DEVINL void g2_st1(float* __restrict__ base, long long off, float v, int bf) {
-    if (bf) ((unsigned short*)base)[off] = (unsigned short)(g2_pack2(v, 0.f) & 0xffffu);
+    if (bf) ((unsigned short*)base)[off] = (unsigned short)(pk2(v, 0.f) & 0xffffu);
     else base[off] = v;
 }
 DEVINL void g2_st4(float* __restrict__ base, long long off, const float v[4], int bf) {
-    if (bf) *(uint2*)((unsigned short*)base + off) = make_uint2(g2_pack2(v[0], v[1]), g2_pack2(v[2], v[3]));
+    if (bf) *(uint2*)((unsigned short*)base + off) = make_uint2(pk2(v[0], v[1]), pk2(v[2], v[3]));
     else *(float4*)(base + off) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
@@ -416,8 +407,8 @@ __global__ __launch_bounds__(256, (BN == 128 && BF >= 2) ? kG2Occ128 : 3) void g
                 o.b = pack8(v);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    v[2 * q] -= __uint_as_float(o.w[q] << 16);
-                    v[2 * q + 1] -= __uint_as_float(o.w[q] & 0xffff0000u);
+                    v[2 * q] -= bflo(o.w[q]);
+                    v[2 * q + 1] -= bfhi(o.w[q]);
                 }
                 return o.b;
             };
@@ -638,10 +629,8 @@ __global__ __launch_bounds__(256) void colsum_vec_kernel(const float* __restrict
         for (long long r = r0 + rr; r < r1; r += rpp) {
             if (BF) {
                 const uint4 v = *(const uint4*)((const unsigned short*)X + r * ld + 8 * ch);
-                acc[0] += __uint_as_float(v.x << 16); acc[1] += __uint_as_float(v.x & 0xffff0000u);
-                acc[2] += __uint_as_float(v.y << 16); acc[3] += __uint_as_float(v.y & 0xffff0000u);
-                acc[4] += __uint_as_float(v.z << 16); acc[5] += __uint_as_float(v.z & 0xffff0000u);
-                acc[6] += __uint_as_float(v.w << 16); acc[7] += __uint_as_float(v.w & 0xffff0000u);
+                acc[0] += bflo(v.x); acc[1] += bfhi(v.x); acc[2] += bflo(v.y); acc[3] += bfhi(v.y);
+                acc[4] += bflo(v.z); acc[5] += bfhi(v.z); acc[6] += bflo(v.w); acc[7] += bfhi(v.w);
             } else {
                 const float4 v = *(const float4*)(X + r * ld + 4 * ch);
                 acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w;
@@ -801,7 +790,6 @@ extern "C" int moda_gemm_f32_ex(const moda_gemm_desc* d, void* stream) {
     if (d->a_sum && ak) return MODA_EINVAL;
     a.M = (int)d->M; a.N = (int)d->N; a.K = (int)d->K;
     a.act = d->act; a.accumulate = d->accumulate;
-    auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
     // k-fast operands step along k in units of 4 from a k0 that is a multiple of 32 (offset by K1 for A2);
     // k-slow operands step along m / n in units of 4 from multiples of 128 / 64
     a.vec_a = al16(d->A) && ((ak ? d->sam : d->sak) % 4 == 0) && (ak || d->M % 4 == 0);
@@ -1689,7 +1677,7 @@ __global__ __launch_bounds__(256) void wprep_kernel(WPrepArgs a) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const int r = i / e.ld_dst, c = i - r * e.ld_dst;
         const float v = (r < e.rows && c < e.cols) ? e.src[(long long)r * e.ld + c] : 0.f;
-        e.dst[i] = (unsigned short)(g2_pack2(v, 0.f) & 0xffffu);
+        e.dst[i] = (unsigned short)(pk2(v, 0.f) & 0xffffu);
     }
 }
 
@@ -1723,12 +1711,12 @@ __global__ __launch_bounds__(256) void head_prep_kernel(const float* __restrict_
                 }
             }
         }
-        w[c2] = g2_pack2(v[0], v[1]);
+        w[c2] = pk2(v[0], v[1]);
     }
     *(uint4*)(dzb + m * 32 + 8 * q) = make_uint4(w[0], w[1], w[2], w[3]);
     if (q == 0) {
         const float ds = raw_feat ? 0.f : g[m * ldo + n_out];
-        *(uint4*)(dzd_tail + m * ld_tail) = make_uint4(g2_pack2(ds, 0.f), 0u, 0u, 0u);
+        *(uint4*)(dzd_tail + m * ld_tail) = make_uint4(pk2(ds, 0.f), 0u, 0u, 0u);
     }
 }
 
@@ -1937,7 +1925,7 @@ __global__ __launch_bounds__(256) void embed_rows64_kernel(const float* __restri
         v[e] = r;
     }
     if (BF) {
-        ((uint4*)out)[i] = make_uint4(g2_pack2(v[0], v[1]), g2_pack2(v[2], v[3]), g2_pack2(v[4], v[5]), g2_pack2(v[6], v[7]));
+        ((uint4*)out)[i] = make_uint4(pk2(v[0], v[1]), pk2(v[2], v[3]), pk2(v[4], v[5]), pk2(v[6], v[7]));
     } else {
         ((float4*)out)[2 * i] = make_float4(v[0], v[1], v[2], v[3]);
         ((float4*)out)[2 * i + 1] = make_float4(v[4], v[5], v[6], v[7]);

@@ -1,7 +1,10 @@
-"""Lane-level model of the LDS images of gemm_bf16.hip (no GPU): the [k][row] bf16 image with its 16-byte-chunk swizzle, the
-per-lane addresses of the transposing reads (ds_read_b64_tr_b16) and of the padded k-fast image (ds_read_b128).
+"""Lane-level model of the LDS images of csrc/mfma_tiles.h (no GPU): the [k][row] bf16 image with its 16-byte-chunk swizzle
+(ks_sw), the per-lane addresses of the transposing reads (tr_base + tr_frag: ds_read_b64_tr_b16) and of the padded k-fast image
+(kf_base: ds_read_b128).  The layout is shared by gemm_bf16.hip (k-tiles of 64, k-fast rows of 144 bytes), gemm_x3.hip (k-tiles of
+32, k-fast rows of 80 bytes) and bwd64_chain.hip (the [m][64] tile image, below); bwd256_fused.hip reads through the same tr_frag
+with a swizzle of its own (test_bwd256_layout.py).
 
-Checked here, for both tile widths: every lane's fragment holds exactly the elements v_mfma_f32_32x32x16_bf16 expects
+Checked here, for both tile widths and both k-tile depths: every lane's fragment holds exactly the elements v_mfma_f32_32x32x16_bf16 expects
 (lane l: row l & 31, k = 8 (l >> 5) + j of the 16-deep step), and the reads of a 32-lane half are bank-conflict free.
 The transposing read is modelled as the CDNA4 ISA describes it: within a group of 16 lanes, lane 4q+p supplies the address
 of row q, elements 4p .. 4p+3 of a 4 x 16 block; lane i receives column i of the four rows."""
@@ -10,15 +13,17 @@ import pytest
 
 KT = 64                       # k per tile (gemm_bf16.hip)
 KF_STRIDE = KT * 2 + 16       # bytes per row of the k-fast image
+KT_X3 = 32                    # the same two of gemm_x3.hip: two k-steps per tile, rows of 80 bytes
+KF_STRIDE_X3 = KT_X3 * 2 + 16
 
 
-def ks_sw(T, row):            # chunk swizzle of a [k][T] image (ks_sw in gemm_bf16.hip)
+def ks_sw(T, row):            # chunk swizzle of a [k][T] image (ks_sw<T> in mfma_tiles.h: both GEMM files and, T = 64, bwd64_chain.hip)
     return ((row & 3) << 2) if T == 128 else (((row >> 1) & 1) << 2)
 
 
 def ks_image(X, T):
     """Bytes-as-elements model of the stash: element (k, c) of the tile -> element slot in LDS (2-byte units)."""
-    RB = T * 2
+    RB, KT = T * 2, X.shape[0]
     img = np.full(KT * RB // 2, -1, np.int64)
     for k in range(KT):
         for ch in range(T // 8):
@@ -41,8 +46,8 @@ def tr_read(img, addr_of_lane):
     return out
 
 
-@pytest.mark.parametrize("T", [64, 128])
-def test_transposing_reads_deliver_the_mfma_fragments_without_bank_conflicts(T):
+@pytest.mark.parametrize("T,KT", [(64, KT), (128, KT), (64, KT_X3), (128, KT_X3)], ids=["64", "128", "64-kt32", "128-kt32"])
+def test_transposing_reads_deliver_the_mfma_fragments_without_bank_conflicts(T, KT):
     RB = T * 2
     rng = np.random.default_rng(T)
     X = rng.permutation(KT * T).reshape(KT, T)       # distinct values: any misplaced element shows
@@ -73,17 +78,18 @@ def test_transposing_reads_deliver_the_mfma_fragments_without_bank_conflicts(T):
 
 
 def test_k_fast_image_rows_cover_all_banks():
-    """[row][k] image, rows of 64 k (128 B) padded to 144 B: the ds_read_b128 of 16 consecutive rows (one k half) touches
-    64 distinct banks; lane l reads row l & 31, bytes 32 u + 16 (l >> 5)."""
-    for u in range(4):
-        for h in range(2):
-            for r0 in (0, 16):
-                banks = set()
-                for r in range(r0, r0 + 16):
-                    a = r * KF_STRIDE + 32 * u + 16 * h
-                    assert a % 16 == 0
-                    banks.update(((a // 4) + d) % 64 for d in range(4))
-                assert len(banks) == 64, (u, h, r0)
+    """[row][k] image, rows of 64 k (128 B) padded to 144 B, or of 32 k (64 B) padded to 80 B: the ds_read_b128 of 16
+    consecutive rows (one k half) touches 64 distinct banks; lane l reads row l & 31, bytes 32 u + 16 (l >> 5)."""
+    for kt, stride in ((KT, KF_STRIDE), (KT_X3, KF_STRIDE_X3)):
+        for u in range(kt // 16):
+            for h in range(2):
+                for r0 in (0, 16):
+                    banks = set()
+                    for r in range(r0, r0 + 16):
+                        a = r * stride + 32 * u + 16 * h
+                        assert a % 16 == 0
+                        banks.update(((a // 4) + d) % 64 for d in range(4))
+                    assert len(banks) == 64, (kt, u, h, r0)
 
 
 def test_epilogue_transpose_buffer_is_read_back_in_row_order():
