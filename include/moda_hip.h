@@ -543,6 +543,64 @@ int moda_icp_moments(const float* x0, const float* y, const int32_t* idx, const 
 int moda_sim3_apply(const float* x, const float* rts, int64_t B, int64_t N, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Whole-sequence ICP and metrics without read-backs (pointset_kernels.hip, icpdev_kernels.hip; purely additive entries: no
+ * existing signature changed, so moda_abi_version() stays 11).  Nothing allocates, synchronises or reads back; every launch
+ * goes to `stream`, so an iteration can be captured into a graph.
+ *   y_len (B) int32: cloud b's targets are y[b, :y_len[b]] of the M_max rows it occupies.  The rows behind them are never
+ *          read as candidates, whatever they hold.  y_len[b] >= 1 is the caller's to ensure (the Python side refuses anything
+ *          else): for y_len[b] < 1 the search leaves cloud b's dist2 / idx alone, but moda_icp_moments_ragged skips every
+ *          query of it and writes zero sums, which the later stages take as they are -- pass active[b] = 0 for such a cloud.
+ *   active (B) int32 | NULL: 0 skips cloud b -- its workgroups return before touching LDS or a barrier, and its outputs
+ *          (dist2, idx, sums, out, rts) keep the bits they had.
+ * ------------------------------------------------------------------------ */
+#define MODA_ICP_SOLVE_SWEEPS 4    /* Jacobi sweeps of moda_icp_solve when it is passed sweeps = 0 */
+#define MODA_SEQ_NMETRIC 10        /* doubles per frame of moda_seq_metrics */
+
+/* moda_nn_fwd with ragged targets: the same kernels, the same plan (moda_nn_splits(B, N, M_max)), the same tie rule.  With
+ * y_len[b] == M_max for every b and all clouds active the output is bit-identical to moda_nn_fwd's. */
+int moda_nn_fwd_ragged(const float* x, const float* y, int64_t B, int64_t N, int64_t M_max, const int32_t* y_len,
+                       const int32_t* active, float* dist2, int32_t* idx, uint64_t* keys, void* stream);
+
+/* moda_icp_moments with ragged targets: a query whose idx is outside [0, y_len[b]) is skipped. */
+int moda_icp_moments_ragged(const float* x0, const float* y, const int32_t* idx, const float* xt, int64_t B, int64_t N,
+                            int64_t M_max, const int32_t* y_len, const int32_t* active, double* partials, double* sums,
+                            void* stream);
+
+/* moda_sim3_apply for the active clouds only (the source side is dense, so there is no length to pass). */
+int moda_sim3_apply_masked(const float* x, const float* rts, int64_t B, int64_t N, const int32_t* active, float* out,
+                           void* stream);
+
+/* moda_icp_solve: the alignment step of ICP from sums (B, MODA_ICP_NSUM) of moda_icp_moments over N correspondences, in
+ * float64: mx, my = means; C = sum x0 (x) yn / N - mx (x) my; C = U S V^T by a cyclic one-sided Jacobi of `sweeps` sweeps
+ * (0: MODA_ICP_SOLVE_SWEEPS; at most 64), S descending, S >= 0, U completed to an orthonormal basis whatever the rank
+ * (C == 0: U = V = I); E = (1, 1, det(U V^T)) unless allow_reflection; R = U E V^T; s = trace(S E) / (sum |x0|^2 / N - |mx|^2)
+ * when estimate_scale, else 1; T = my - (s mx) R.  Rounded once to rts (B,13) fp32 = R row-major, T, s: the row
+ * moda_sim3_apply reads.  One lane per cloud.  MODA_ESHAPE for B < 1 or N < 1. */
+int moda_icp_solve(const double* sums, int64_t B, int64_t N, int32_t estimate_scale, int32_t allow_reflection, int32_t sweeps,
+                   const int32_t* active, float* rts, void* stream);
+
+/* moda_icp_advance: the stopping rule of the ICP loop for the active clouds, from sums[b][16] = sum |xt - yn|^2:
+ *   r = sqrt(sums[b][16] / N); relative = 1 when iterations[b] == 0, else (prev - r) / prev, and 0 where prev == 0;
+ *   prev_rmse[b] = r (float64), rmse[b] = r (fp32), iterations[b] += 1; a cloud has converged when relative <= thr.
+ * per_element != 0: converged[b] is set and active[b] cleared for every cloud that has converged itself -- it gets what it
+ * would get in a batch of one.  per_element == 0 (pytorch3d's rule): nothing changes until every active cloud has converged
+ * in the same iteration; then all of them are marked converged and cleared.  flags[0] = 1 while some cloud is still active,
+ * else 0.  The caller initialises iterations = 0, converged = 0, active = 1.  One workgroup. */
+int moda_icp_advance(const double* sums, int64_t B, int64_t N, double relative_rmse_thr, int32_t per_element, double* prev_rmse,
+                     float* rmse, int32_t* iterations, int32_t* converged, int32_t* active, int32_t* flags, void* stream);
+
+/* moda_seq_metrics: the figures render_vis.py:399-411 prints, per frame, from the two squared-distance arrays of a Chamfer
+ * pass: dist_gt (B,M_max) (ground truth -> prediction; the first y_len[b] rows count, y_len NULL: all) and dist_pred (B,N)
+ * (prediction -> ground truth).  out (B, MODA_SEQ_NMETRIC) float64:
+ *   [0] cd = mean sqrt(dist_gt) + mean sqrt(dist_pred) (fp32 square roots, float64 sums and quotients)
+ *   [1..3] the F-score at thresholds fp32((bbox_max[b] * {0.01, 0.02, 0.05})^2), the product and square taken in float64
+ *   [4..9] (precision_1, precision_2) at each threshold
+ * with fscore's quotient rule: every quotient is formed in float64 from its fp32 operands and rounded once to fp32; 0 / 0
+ * is 0.  Integer counts and float64 sums over a fixed tree, one workgroup per frame: bit-identical from run to run. */
+int moda_seq_metrics(const float* dist_gt, const float* dist_pred, int64_t B, int64_t M_max, int64_t N, const int32_t* y_len,
+                     const float* bbox_max, double* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Bone re-initialisation and surface sampling on the rest mesh (moda_amd/csrc/bones_kernels.hip; additive entries of ABI 9: no
  * existing signature changed).  None of these reads anything back; the caller reads `state` / `n_bad` when it needs them.
  * ------------------------------------------------------------------------ */

@@ -18,7 +18,7 @@ from . import mesh  # noqa: F401
 from .mesh import TriMesh, marching_cubes, largest_part, extract_mesh  # noqa: F401
 from . import mesh_eval  # noqa: F401
 from .mesh_eval import (nearest, chamfer_3DDist, fscore, iterative_closest_point, eval_mesh, ICPSolution,  # noqa: F401
-                        SimilarityTransform)
+                        SimilarityTransform, iterative_closest_point_device, eval_sequence, SequenceEval)
 from . import bones  # noqa: F401
 from .bones import kmeans, sample_points_from_meshes, sample_surface, KMeansResult  # noqa: F401
 from . import mesh_render  # noqa: F401

@@ -199,6 +199,14 @@ _SIGNATURES = {
     "moda_maxpool3x3s2_nhwc": (_c.c_int, [_P, _I64, _I64, _I64, _I64, _P, _P]),
     "moda_posecnn_input": (_c.c_int, [_P, _I64, _I64, _I64, _I64, _I64, _I32, _P, _P]),
     "moda_posecnn_tail": (_c.c_int, [_P, _I64, _I64, _I64, _P, _P]),
+    # whole-sequence ICP and metrics: ragged / masked point-set launches, the alignment solve, the stopping rule, the metrics row
+    # (pointset_kernels.hip, icpdev_kernels.hip): additive, the ABI stays 11
+    "moda_nn_fwd_ragged": (_c.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "moda_icp_moments_ragged": (_c.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
+    "moda_sim3_apply_masked": (_c.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
+    "moda_icp_solve": (_c.c_int, [_P, _I64, _I64, _I32, _I32, _I32, _P, _P, _P]),
+    "moda_icp_advance": (_c.c_int, [_P, _I64, _I64, _c.c_double, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "moda_seq_metrics": (_c.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -19,6 +19,10 @@
 //               combined with atomicMin: minimum distance, then lowest index, whatever order the workgroups finish in.
 //   moments     per-thread float64 sums, a fixed shuffle / LDS tree per workgroup, partials added in index order by a second
 //               kernel: no float atomics, the same bits on every run.
+//   ragged      moda_nn_fwd_ragged / moda_icp_moments_ragged / moda_sim3_apply_masked run the SAME kernels with two more pointers:
+//               y_len[b] (only y[b, :y_len[b]] are targets: the tile load stops there, so padding rows are never read as
+//               candidates, whatever they hold) and active[b] (0: every workgroup of cloud b returns before it touches LDS or
+//               a barrier, and that cloud's outputs keep their bits).  The dense entries pass NULL for both.
 // Device memory is written only by plain vector stores and HIP atomic functions.  Indices are int32 (the entry points refuse
 // B * N or B * M >= 2^31); element offsets are formed in 64 bits.
 #include <hip/hip_runtime.h>
@@ -60,14 +64,20 @@ DEVINL float dist2_1(float qx, float qy, float qz, float tx, float ty, float tz)
 
 // splits > 1: results go to keys through atomicMin; splits == 1: dist2 / idx are written directly
 __global__ __launch_bounds__(kBlock) void nn_kernel(const float* __restrict__ x, const float* __restrict__ y, int N, int M,
-                                                    int nblk, int splits, int range, float* __restrict__ dist2,
+                                                    int nblk, int splits, int range, const int* __restrict__ y_len,
+                                                    const int* __restrict__ active, float* __restrict__ dist2,
                                                     int* __restrict__ idx, unsigned long long* __restrict__ keys) {
     __shared__ __attribute__((aligned(16))) float lds[3][kTile];
     const int t = threadIdx.x;
     const int per_b = nblk * splits;
     const int b = blockIdx.x / per_b, r = blockIdx.x - b * per_b;
+    if (active && !active[b]) return;                                       // a skipped cloud: before any LDS access or barrier
     const int s = r / nblk, qb = r - s * nblk;
-    const int m_begin = s * range, m_end = min(M, m_begin + range);        // the host makes every range non-empty
+    // dense: the host makes every range non-empty.  ragged: y has M rows per cloud of which the first y_len[b] are targets; a
+    // range that begins past them has no candidate and leaves its keys alone (block-uniform, before the first barrier)
+    const int len = y_len ? min(y_len[b], M) : M;
+    const int m_begin = s * range, m_end = min(len, m_begin + range);
+    if (m_begin >= m_end) return;
     const float* xb = x + (int64_t)b * N * 3;
     const float* yb = y + (int64_t)b * M * 3;
     const int q0 = qb * kQB + t;
@@ -140,10 +150,12 @@ __global__ __launch_bounds__(kBlock) void nn_kernel(const float* __restrict__ x,
     }
 }
 
-__global__ __launch_bounds__(kBlock) void nn_unpack_kernel(const unsigned long long* __restrict__ keys, int64_t n,
+__global__ __launch_bounds__(kBlock) void nn_unpack_kernel(const unsigned long long* __restrict__ keys, int64_t n, int N,
+                                                           const int* __restrict__ y_len, const int* __restrict__ active,
                                                            float* __restrict__ dist2, int* __restrict__ idx) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
+    if ((active && !active[i / N]) || (y_len && y_len[i / N] < 1)) return;  // no search ran: dist2 / idx keep their bits
     const unsigned long long k = keys[i];
     dist2[i] = __uint_as_float((unsigned)(k >> 32));
     idx[i] = (int)(unsigned)k;
@@ -171,9 +183,12 @@ __global__ __launch_bounds__(kBlock) void chamfer_bwd_kernel(const float* __rest
 // partial sums of one workgroup: k < 16 the moments (x0 non-null), k == 16 the squared residual (xt non-null)
 __global__ __launch_bounds__(kBlock) void icp_partial_kernel(const float* __restrict__ x0, const float* __restrict__ y,
                                                              const int* __restrict__ idx, const float* __restrict__ xt, int N,
-                                                             int M, int nblk, double* __restrict__ partials) {
+                                                             int M, int nblk, const int* __restrict__ y_len,
+                                                             const int* __restrict__ active, double* __restrict__ partials) {
     __shared__ double lds[kBlock / 64][kNSum];
     const int b = blockIdx.x / nblk, k = blockIdx.x - b * nblk;
+    if (active && !active[b]) return;                                       // skipped: icp_final_kernel skips it as well
+    const int len = y_len ? min(y_len[b], M) : M;                           // ragged: an index into the padding is a bad index
     const int64_t ob = (int64_t)b * N;
     const float* yb = y + (int64_t)b * M * 3;
     double acc[kNSum];
@@ -181,7 +196,7 @@ __global__ __launch_bounds__(kBlock) void icp_partial_kernel(const float* __rest
     for (int q = 0; q < kNSum; ++q) acc[q] = 0.0;
     for (int i = k * kBlock + threadIdx.x; i < N; i += nblk * kBlock) {
         const int j = idx[ob + i];
-        if (j < 0 || j >= M) continue;
+        if (j < 0 || j >= len) continue;
         const double ty[3] = {(double)yb[(int64_t)j * 3 + 0], (double)yb[(int64_t)j * 3 + 1], (double)yb[(int64_t)j * 3 + 2]};
         if (x0) {
             const double p[3] = {(double)x0[(ob + i) * 3 + 0], (double)x0[(ob + i) * 3 + 1], (double)x0[(ob + i) * 3 + 2]};
@@ -220,9 +235,9 @@ __global__ __launch_bounds__(kBlock) void icp_partial_kernel(const float* __rest
 }
 
 __global__ __launch_bounds__(64) void icp_final_kernel(const double* __restrict__ partials, int nblk, int has_x0, int has_xt,
-                                                       double* __restrict__ out) {
+                                                       const int* __restrict__ active, double* __restrict__ out) {
     const int q = threadIdx.x;
-    if (q >= kNSum || (q < 16 ? !has_x0 : !has_xt)) return;
+    if (q >= kNSum || (q < 16 ? !has_x0 : !has_xt) || (active && !active[blockIdx.x])) return;
     const double* p = partials + (int64_t)blockIdx.x * nblk * kNSum;
     double v = 0.0;
     for (int k = 0; k < nblk; ++k) v += p[(int64_t)k * kNSum + q];          // index order: the same bits on every run
@@ -230,9 +245,11 @@ __global__ __launch_bounds__(64) void icp_final_kernel(const double* __restrict_
 }
 
 __global__ __launch_bounds__(kBlock) void sim3_apply_kernel(const float* __restrict__ x, const float* __restrict__ rts,
-                                                            int64_t total, int N, float* __restrict__ out) {
+                                                            int64_t total, int N, const int* __restrict__ active,
+                                                            float* __restrict__ out) {
     const int64_t o = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (o >= total) return;
+    if (active && !active[o / N]) return;                                   // skipped: out keeps its bits
     const float* p = rts + (o / N) * 13;
     const float a = x[o * 3 + 0], b = x[o * 3 + 1], c = x[o * 3 + 2], s = p[12];
 #pragma unroll
@@ -271,8 +288,10 @@ extern "C" int32_t moda_nn_splits(int64_t B, int64_t N, int64_t M, int64_t* rang
     return splits;
 }
 
-extern "C" int moda_nn_fwd(const float* x, const float* y, int64_t B, int64_t N, int64_t M, float* dist2, int32_t* idx,
-                           uint64_t* keys, void* stream) {
+// the dense entry passes y_len = active = NULL: one launcher, so the ragged route with full lengths runs the same plan and the
+// same instructions as the dense one
+static int nn_launch(const float* x, const float* y, int64_t B, int64_t N, int64_t M, const int32_t* y_len, const int32_t* active,
+                     float* dist2, int32_t* idx, uint64_t* keys, void* stream) {
     if (!ps_shape_ok(B, N, M)) return MODA_ESHAPE;
     if (N == 0) return 0;
     if (!x || !y || !dist2 || !idx) return MODA_EINVAL;
@@ -288,11 +307,22 @@ extern "C" int moda_nn_fwd(const float* x, const float* y, int64_t B, int64_t N,
         if (e != hipSuccess) return (int)e;
     }
     hipLaunchKernelGGL(nn_kernel, dim3((unsigned)(B * nblk * splits)), dim3(kBlock), 0, st, x, y, (int)N, (int)M, nblk, splits,
-                       range, dist2, idx, (unsigned long long*)keys);
+                       range, y_len, active, dist2, idx, (unsigned long long*)keys);
     if (splits > 1)
         hipLaunchKernelGGL(nn_unpack_kernel, dim3(nblocks(B * N, kBlock)), dim3(kBlock), 0, st, (const unsigned long long*)keys,
-                           B * N, dist2, idx);
+                           B * N, (int)N, y_len, active, dist2, idx);
     return (int)hipGetLastError();
+}
+
+extern "C" int moda_nn_fwd(const float* x, const float* y, int64_t B, int64_t N, int64_t M, float* dist2, int32_t* idx,
+                           uint64_t* keys, void* stream) {
+    return nn_launch(x, y, B, N, M, nullptr, nullptr, dist2, idx, keys, stream);
+}
+
+extern "C" int moda_nn_fwd_ragged(const float* x, const float* y, int64_t B, int64_t N, int64_t M_max, const int32_t* y_len,
+                                  const int32_t* active, float* dist2, int32_t* idx, uint64_t* keys, void* stream) {
+    if (ps_shape_ok(B, N, M_max) && N > 0 && !y_len) return MODA_EINVAL;
+    return nn_launch(x, y, B, N, M_max, y_len, active, dist2, idx, keys, stream);
 }
 
 extern "C" int moda_chamfer_bwd(const float* x, const float* y, const int32_t* idx, const float* grad_dist, int64_t B, int64_t N,
@@ -305,25 +335,46 @@ extern "C" int moda_chamfer_bwd(const float* x, const float* y, const int32_t* i
     return (int)hipGetLastError();
 }
 
-extern "C" int moda_icp_moments(const float* x0, const float* y, const int32_t* idx, const float* xt, int64_t B, int64_t N,
-                                int64_t M, double* partials, double* sums, void* stream) {
+static int icp_moments_launch(const float* x0, const float* y, const int32_t* idx, const float* xt, int64_t B, int64_t N, int64_t M,
+                              const int32_t* y_len, const int32_t* active, double* partials, double* sums, void* stream) {
     if (!ps_shape_ok(B, N, M) || N < 1) return MODA_ESHAPE;
     const int nblk = (int)((N + kQB - 1) / kQB) < kIcpMaxBlocks ? (int)((N + kQB - 1) / kQB) : kIcpMaxBlocks;
     if ((double)B * nblk >= 2147483648.0) return MODA_ESHAPE;
     if (!y || !idx || (!x0 && !xt) || !partials || !sums) return MODA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(icp_partial_kernel, dim3((unsigned)(B * nblk)), dim3(kBlock), 0, st, x0, y, idx, xt, (int)N, (int)M, nblk,
-                       partials);
+                       y_len, active, partials);
     hipLaunchKernelGGL(icp_final_kernel, dim3((unsigned)B), dim3(64), 0, st, (const double*)partials, nblk, x0 ? 1 : 0, xt ? 1 : 0,
-                       sums);
+                       active, sums);
     return (int)hipGetLastError();
 }
 
-extern "C" int moda_sim3_apply(const float* x, const float* rts, int64_t B, int64_t N, float* out, void* stream) {
+extern "C" int moda_icp_moments(const float* x0, const float* y, const int32_t* idx, const float* xt, int64_t B, int64_t N,
+                                int64_t M, double* partials, double* sums, void* stream) {
+    return icp_moments_launch(x0, y, idx, xt, B, N, M, nullptr, nullptr, partials, sums, stream);
+}
+
+extern "C" int moda_icp_moments_ragged(const float* x0, const float* y, const int32_t* idx, const float* xt, int64_t B, int64_t N,
+                                       int64_t M_max, const int32_t* y_len, const int32_t* active, double* partials, double* sums,
+                                       void* stream) {
+    if (ps_shape_ok(B, N, M_max) && N >= 1 && !y_len) return MODA_EINVAL;
+    return icp_moments_launch(x0, y, idx, xt, B, N, M_max, y_len, active, partials, sums, stream);
+}
+
+static int sim3_launch(const float* x, const float* rts, int64_t B, int64_t N, const int32_t* active, float* out, void* stream) {
     if (B < 1 || N < 0 || (double)B * (double)N >= 2147483648.0) return MODA_ESHAPE;
     if (N == 0) return 0;
     if (!x || !rts || !out) return MODA_EINVAL;
     hipLaunchKernelGGL(sim3_apply_kernel, dim3(nblocks(B * N, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, x, rts, B * N, (int)N,
-                       out);
+                       active, out);
     return (int)hipGetLastError();
+}
+
+extern "C" int moda_sim3_apply(const float* x, const float* rts, int64_t B, int64_t N, float* out, void* stream) {
+    return sim3_launch(x, rts, B, N, nullptr, out, stream);
+}
+
+extern "C" int moda_sim3_apply_masked(const float* x, const float* rts, int64_t B, int64_t N, const int32_t* active, float* out,
+                                      void* stream) {
+    return sim3_launch(x, rts, B, N, active, out, stream);
 }
