@@ -29,8 +29,6 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kStage = kBlock * 3;                  // floats of one staging buffer: 192 per wave
 static_assert(kBlock % 64 == 0 && MODA_ANIM_MAX_BONES == 64, "whole waves; the instantiations below are 16, 32, 48 and 64 bones");
 
-inline unsigned nblocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
-
 // LDS: [kTile x NB x 2] float4 (the tile's dual quaternions, bones B .. NB - 1 of a frame zero) | [2 x kStage] floats (output
 // staging, two buffers so that one barrier a frame orders a wave's writes before its reads; a wave only ever touches its own
 // 192 floats of a buffer).  NB = B rounded up to 16: the bone loop is unrolled without a branch (the weights need static

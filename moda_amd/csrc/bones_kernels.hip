@@ -8,7 +8,7 @@
 //               strict <, in index order: lowest index among equal distances.  d = fma(dz, dz, fma(dy, dy, dx * dx)), every
 //               operation rounded on its own in fp32 (contraction is off for this file), as in pointset_kernels.hip.
 //               Sums: a wave handles 64 points at a time; for each cluster present in the batch (ballot) the members' x, y, z
-//               are widened to float64 and added over the wave by a butterfly (__shfl_xor 32..1, non-members contribute 0),
+//               are widened to float64 and added over the wave by wave_add's butterfly (__shfl_xor 32..1, non-members contribute 0),
 //               the count is the ballot's popcount, and lane k adds the batch's result to ITS registers: lane k of a wave
 //               owns cluster k.  Batches follow in index order, the four waves are added in wave order through LDS, the
 //               workgroups (at most MODA_KMEANS_MAX_BLOCKS, grid-stride) write partials (blocks, K, 4).  No float atomics: for
@@ -19,19 +19,18 @@
 //               the host enqueues several iterations and reads the flag back once.
 //   sampling    face areas in fp32 (faces with an index outside [0, V) are counted, given area 0 and never read through), an
 //               inclusive float64 prefix sum of the areas (tile sums, one workgroup scanning the tile sums, tile scans: the
-//               structure of mesh_kernels.hip, no atomics), then one lane per sample: binary search for the first face whose
+//               structure of mesh_kernels.hip on the same block_scan, no atomics), then one lane per sample: binary search for the first face whose
 //               CDF exceeds u0 * total, and the point at pytorch3d's barycentrics.
 // Device memory is written only by plain vector stores and HIP atomic functions.  Indices are int32; offsets in 64 bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-#define DEVINL __device__ __forceinline__
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
@@ -41,8 +40,6 @@ constexpr int kPerThread = 8;
 constexpr int kTile = kBlock * kPerThread;           // MODA_MC_SCAN_TILE
 static_assert(kTile == MODA_MC_SCAN_TILE, "scan tile");
 static_assert(4 * kMaxK <= kBlock && kMaxK <= 64, "one lane per cluster, one thread per (cluster, sum)");
-
-inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 DEVINL float dist2_1(float qx, float qy, float qz, float tx, float ty, float tz) {
     const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
@@ -99,13 +96,8 @@ __global__ __launch_bounds__(kBlock) void kmeans_assign_kernel(const float* __re
             const bool mine = a == k;
             const unsigned long long m = __ballot(mine);
             if (!m) continue;                                               // wave-uniform
-            double vx = mine ? (double)px : 0.0, vy = mine ? (double)py : 0.0, vz = mine ? (double)pz : 0.0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                vx += __shfl_xor(vx, o);
-                vy += __shfl_xor(vy, o);
-                vz += __shfl_xor(vz, o);
-            }
+            const double vx = wave_add(mine ? (double)px : 0.0), vy = wave_add(mine ? (double)py : 0.0),
+                         vz = wave_add(mine ? (double)pz : 0.0);
             if (lane == k) {
                 ax += vx;
                 ay += vy;
@@ -209,27 +201,10 @@ __global__ __launch_bounds__(kBlock) void face_area_kernel(const float* __restri
     areas[f] = 0.5f * sqrtf((cx * cx + cy * cy) + cz * cz);
 }
 
-// exclusive scan of one value per thread across the block, in a fixed order; *total = the block's sum
-DEVINL double block_exclusive_scan(double v, double* lds, double* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
-    const double prev = __shfl_up(v, 1);
-    if (lane == 63) lds[w] = v;
-    __syncthreads();
-    double before = 0.0, all = 0.0;
-#pragma unroll
-    for (int q = 0; q < kWaves; ++q) {
-        const double s = lds[q];
-        if (q < w) before += s;
-        all += s;
-    }
-    __syncthreads();
-    *total = all;
-    return lane == 0 ? before : before + prev;
+// the exclusive value of a block_scan: the earlier waves' sum first, then the wave's own earlier lanes -- this association is the CDF's
+DEVINL double scan_exclusive(const BlockScan<double>& r) {
+    const double prev = __shfl_up(r.incl_wave, 1);
+    return (threadIdx.x & 63) == 0 ? r.before : r.before + prev;
 }
 
 __global__ __launch_bounds__(kBlock) void cdf_tile_sum_kernel(const float* __restrict__ areas, int n, double* __restrict__ tile_sum) {
@@ -239,36 +214,20 @@ __global__ __launch_bounds__(kBlock) void cdf_tile_sum_kernel(const float* __res
 #pragma unroll
     for (int q = 0; q < kPerThread; ++q)
         if (base + q < n) s += (double)areas[base + q];
-    double total;
-    block_exclusive_scan(s, lds, &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+    const BlockScan<double> r = block_scan<double, kWaves>(s, lds);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = r.total;
 }
 
 // one block: exclusive scan of the tile sums
 __global__ __launch_bounds__(1024) void cdf_tiles_kernel(const double* __restrict__ tile_sum, int nt, double* __restrict__ tile_off) {
     __shared__ double lds[1024 / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     double carry = 0.0;
     for (int b0 = 0; b0 < nt; b0 += 1024) {
         const int b = b0 + (int)threadIdx.x;
-        double v = b < nt ? tile_sum[b] : 0.0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const double u = __shfl_up(v, o);
-            if (lane >= o) v += u;
-        }
-        const double prev = __shfl_up(v, 1);
-        if (lane == 63) lds[w] = v;
-        __syncthreads();
-        double before = 0.0, all = 0.0;
-        for (int q = 0; q < 1024 / 64; ++q) {
-            const double s = lds[q];
-            if (q < w) before += s;
-            all += s;
-        }
-        if (b < nt) tile_off[b] = carry + (lane == 0 ? before : before + prev);
-        carry += all;
-        __syncthreads();
+        const BlockScan<double> r = block_scan<double, 1024 / 64>(b < nt ? tile_sum[b] : 0.0, lds);
+        const double excl = scan_exclusive(r);
+        if (b < nt) tile_off[b] = carry + excl;
+        carry += r.total;
     }
 }
 
@@ -283,8 +242,7 @@ __global__ __launch_bounds__(kBlock) void cdf_tile_kernel(const float* __restric
         c[q] = base + q < n ? (double)areas[base + q] : 0.0;
         s += c[q];
     }
-    double total;
-    double run = tile_off[blockIdx.x] + block_exclusive_scan(s, lds, &total);
+    double run = tile_off[blockIdx.x] + scan_exclusive(block_scan<double, kWaves>(s, lds));
 #pragma unroll
     for (int q = 0; q < kPerThread; ++q) {
         run += c[q];

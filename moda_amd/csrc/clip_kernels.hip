@@ -9,7 +9,7 @@
 //              where the segment's base is 16-byte aligned, four bounds-checked scalar loads otherwise and in the tail quad, the
 //              SAME element-to-lane map either way, so a norm does not depend on where its tensors lie.  Each square is rounded
 //              in fp32 (contraction is off for this file), widened to float64 and added in element order per lane, over the wave
-//              by a butterfly (__shfl_xor 32..1), over the four waves in wave order through LDS.  NaN and +-inf elements are
+//              by wave_add's butterfly (__shfl_xor 32..1), over the four waves in wave order through LDS.  NaN and +-inf elements are
 //              counted separately.  A frozen chunk (its group's byte or its segment's) is scanned for non-finite values like any
 //              other -- the reference tests for NaN before it freezes -- but contributes 0 to the sum.
 //   finalize   one workgroup.  Wave w takes groups w, w + 4, ...: the group's partials are added strictly in table order (64 are
@@ -23,12 +23,11 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-#define DEVINL __device__ __forceinline__
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
@@ -117,12 +116,9 @@ __global__ __launch_bounds__(kBlock) void clip_partial_kernel(Tables T, double* 
             if (!k.frozen) acc += (double)sq;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        acc += __shfl_xor(acc, o);
-        n_nan += __shfl_xor(n_nan, o);
-        n_inf += __shfl_xor(n_inf, o);
-    }
+    acc = wave_add(acc);
+    n_nan = wave_add(n_nan);
+    n_inf = wave_add(n_inf);
     if (lane == 0) {
         red[w] = acc;
         red_n[w][0] = n_nan;
@@ -156,11 +152,8 @@ __global__ __launch_bounds__(kBlock) void clip_finalize_kernel(const double* __r
         n_nan += nonfinite[2 * c];
         n_inf += nonfinite[2 * c + 1];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        n_nan += __shfl_xor(n_nan, o);
-        n_inf += __shfl_xor(n_inf, o);
-    }
+    n_nan = wave_add(n_nan);
+    n_inf = wave_add(n_inf);
     if (lane == 0) {
         red_n[w][0] = n_nan;
         red_n[w][1] = n_inf;

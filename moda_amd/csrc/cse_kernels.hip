@@ -30,12 +30,12 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kBlock = 256;
@@ -45,8 +45,6 @@ constexpr int kCT = MODA_CSE_CAND_TILE;          // candidates per LDS tile
 constexpr int kCTP = kCT + 4;                    // plane stride: the (k, m) writes of row-major candidates hit 64 banks
 constexpr int kTargetBlocks = 1024;              // four workgroups per CU on 256 CUs
 constexpr int kOodMaxBlocks = MODA_OOD_MAX_BLOCKS;
-
-inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 DEVINL unsigned long long make_key(float s, int j) {
     unsigned u;
@@ -287,12 +285,9 @@ __global__ __launch_bounds__(kBlock) void ood_partial_kernel(const int* __restri
         cnt += 1.0;
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_down(sum, o);
-        cnt += __shfl_down(cnt, o);
-        bad += __shfl_down(bad, o);
-    }
+    sum = wave_add_down(sum);
+    cnt = wave_add_down(cnt);
+    bad = wave_add_down(bad);
     if (lane == 0) {
         lds[wv][0] = sum;
         lds[wv][1] = cnt;

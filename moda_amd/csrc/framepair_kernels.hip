@@ -24,17 +24,14 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
-
 constexpr int kBlock = 256;
 constexpr int kBboxMaxBlocks = 1024;             // workgroups per frame of the box reduction
-
-inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // ---- the sampler ------------------------------------------------------------------------------------------------------------
 struct Taps {
@@ -145,13 +142,12 @@ __global__ __launch_bounds__(kBlock) void bbox_kernel(const void* __restrict__ m
             if (on) box_add(bx, p, w);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        bx.x0 = min(bx.x0, __shfl_xor(bx.x0, o));
-        bx.x1 = max(bx.x1, __shfl_xor(bx.x1, o));
-        bx.y0 = min(bx.y0, __shfl_xor(bx.y0, o));
-        bx.y1 = max(bx.y1, __shfl_xor(bx.y1, o));
-    }
+    const auto lower = [](int x, int y) { return min(x, y); };
+    const auto upper = [](int x, int y) { return max(x, y); };
+    bx.x0 = wave_all(bx.x0, lower);
+    bx.x1 = wave_all(bx.x1, upper);
+    bx.y0 = wave_all(bx.y0, lower);
+    bx.y1 = wave_all(bx.y1, upper);
     if ((threadIdx.x & 63) == 0 && bx.x1 >= 0) {
         atomicMin(&box[b * 4 + 0], bx.x0);
         atomicMax(&box[b * 4 + 1], bx.x1);

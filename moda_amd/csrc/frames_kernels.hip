@@ -9,12 +9,12 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
 constexpr int kBlock = 256;               // the block kernel: four waves a (frame, point range)
 constexpr int kWave = 64;
 constexpr int kSmallBlock = 64;           // the small-N kernel and the scatter: one lane a frame / batch entry
@@ -118,12 +118,9 @@ __global__ void near_far_block_kernel(const float* __restrict__ pts, long long N
     const long long lo = (long long)s * per, hi = (lo + per < N) ? lo + per : N;
     Range a = {__uint_as_float(0x7f800000u), __uint_as_float(0xff800000u), 0};
     for (long long i = lo + threadIdx.x; i < hi; i += kBlock) take(a, depth(p, pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]));
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        a.lo = fminf(a.lo, __shfl_xor(a.lo, off, kWave));
-        a.hi = fmaxf(a.hi, __shfl_xor(a.hi, off, kWave));
-        a.nan |= __shfl_xor(a.nan, off, kWave);
-    }
+    a.lo = wave_all(a.lo, [](float x, float y) { return fminf(x, y); });
+    a.hi = wave_all(a.hi, [](float x, float y) { return fmaxf(x, y); });
+    a.nan = wave_all(a.nan, [](int x, int y) { return x | y; });
     const int wave = threadIdx.x / kWave;
     if ((threadIdx.x & (kWave - 1)) == 0) {
         sh_lo[wave] = a.lo;
@@ -197,8 +194,6 @@ __global__ void frames_scatter_kernel(const float* __restrict__ rtk, const float
     for (int i = 0; i < 12; ++i) rd[i] = rs[i];
     tab_idk[f] = 1.f;
 }
-
-inline unsigned nblocks(long long n, int block) { return (unsigned)((n + block - 1) / block); }
 
 inline int auto_splits(long long N, long long M) {
     if (N <= kSmallN) return 1;

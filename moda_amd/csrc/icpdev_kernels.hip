@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
@@ -219,13 +220,10 @@ __global__ __launch_bounds__(kBlock) void seq_metrics_kernel(const float* __rest
         for (int k = 0; k < 3; ++k) c[2 * k + 1] += d < thr[k] ? 1 : 0;
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    s1 = wave_add_down(s1);
+    s2 = wave_add_down(s2);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_down(s1, o);
-        s2 += __shfl_down(s2, o);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) c[k] += __shfl_down(c[k], o);
-    }
+    for (int k = 0; k < 6; ++k) c[k] = wave_add_down(c[k]);
     if (lane == 0) {
         lds_s[w][0] = s1;
         lds_s[w][1] = s2;

@@ -7,11 +7,12 @@
 //               order the rays arrive in: the highest ray index wins a slot, as numpy's fancy assignment leaves it.
 //       rows    one wavefront per frame: every slot of the frame's row takes its owner's value (and gives the owner word back as
 //               -1, the state `owner` is in between calls), the row's sum is formed in float64 -- lane l adds the slots l, l + 64,
-//               ... in order, the lanes are joined by the xor butterfly 32..1 -- and mean = sum / (1e-9 + #positive).
+//               ... in order, the lanes are joined by the xor butterfly 32..1 (wave_add) -- and mean = sum / (1e-9 + #positive).
 //       final   one workgroup: the median of the positive means by exact ranking (ties broken by the frame index), the frames'
 //               flags mean > median * scale_factor in float64, invalid[i] = flag[frameid[i]] and the status counters.
 //   loss filter, frame mode  (:447-476 loss_filter + the state update of moda.py:533)  one launch of one workgroup.
-//   root smoothness          (:486-517 compute_root_sm_2nd_loss, geom_utils.py:1196-1205 rot_angle)  one workgroup forward; the
+//   root smoothness          (:486-517 compute_root_sm_2nd_loss, geom_utils.py:1196-1205 rot_angle)  one workgroup forward (the pose
+//               helpers and block_sums of pose_loss.h, shared with the first-order loss of warmup_kernels.hip); the
 //               backward is a gather: one thread per frame sums the up to three triples the frame belongs to, in a fixed order.
 //   loss assembly            (moda.py:517-768)  total <- carry_t * total + weight_t * mean_t over the terms in order, times total_wt:
 //               one wavefront per term forward, one launch backward.  loss_utils.total_loss (no scale / drop / carry) and
@@ -22,26 +23,11 @@
 
 #include "moda_hip.h"
 #include "moda_dev.h"
+#include "pose_loss.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-DEVINL long long load_id(const void* p, int is64, long long i) {
-    return is64 ? (long long)((const int64_t*)p)[i] : (long long)((const int32_t*)p)[i];
-}
-
-DEVINL double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-DEVINL int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- loss filter ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void flt_claim_kernel(const void* __restrict__ errid, int e64, int N, long long slots,
@@ -73,8 +59,8 @@ __global__ __launch_bounds__(256) void flt_rows_kernel(const float* __restrict__
         s += (double)x;
         c += x > 0.f ? 1 : 0;
     }
-    s = wave_sum_f64(s);
-    c = wave_sum_i32(c);
+    s = wave_add(s);
+    c = wave_add(c);
     if (lane == 0) mean[f] = s / (1e-9 + (double)c);
 }
 
@@ -156,8 +142,8 @@ __global__ __launch_bounds__(1024) void flt_frame_kernel(const float* __restrict
             s += (double)(x[e] * mf);
             ms += (double)mf;
         }
-        s = wave_sum_f64(s);
-        ms = wave_sum_f64(ms);
+        s = wave_add(s);
+        ms = wave_add(ms);
         if (lane == 0) flo_err[b] = (float)s / (1e-9f + (float)ms);
     }
     // the median of the history BEFORE this step's update (median_positive's barriers also publish flo_err to the workgroup)
@@ -184,18 +170,6 @@ __global__ __launch_bounds__(1024) void flt_frame_kernel(const float* __restrict
 }
 
 // ---- root smoothness -----------------------------------------------------------------------------------------------------
-// torch's clamp(-1 + eps, 1 - eps) on an fp32 tensor: the bounds are formed in double and rounded to fp32 once
-constexpr float kCosLo = (float)(-1.0 + 1e-4), kCosHi = (float)(1.0 - 1e-4);
-
-DEVINL void load_pose(const float* __restrict__ rtk, int stride, long long f, float R[9], float t[3]) {
-    const float* p = rtk + f * stride;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float4 r = *reinterpret_cast<const float4*>(p + 4 * i);       // rows of 4 floats, 16-byte aligned (host-checked)
-        R[3 * i] = r.x; R[3 * i + 1] = r.y; R[3 * i + 2] = r.z; t[i] = r.w;
-    }
-}
-
 // C = X Y^T, each entry the products k = 0, 1, 2 added in that order
 DEVINL void mul_abt(const float X[9], const float Y[9], float C[9]) {
 #pragma unroll
@@ -216,24 +190,10 @@ DEVINL void triple_eval(const float* __restrict__ rtk, int stride, long long j, 
     load_pose(rtk, stride, j + 2, q.R2, t2);
     mul_abt(q.R0, q.R1, q.A);                                     // rot_sub1 = R0 R1^T
     mul_abt(q.R1, q.R2, q.B);                                     // rot_sub2 = R1 R2^T
-    float tr = 0.f;                                               // trace of rot_sub1 rot_sub2^T: its diagonal, then 00 + 11 + 22
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float rii = q.A[3 * i] * q.B[3 * i] + q.A[3 * i + 1] * q.B[3 * i + 1] + q.A[3 * i + 2] * q.B[3 * i + 2];
-        tr = i == 0 ? rii : tr + rii;
-    }
-    q.cosv = (tr - 1.f) / 2.f;
+    q.cosv = cos_of(q.A, q.B);                                    // from the trace of rot_sub1 rot_sub2^T
 #pragma unroll
     for (int c = 0; c < 3; ++c) q.d[c] = (t0[c] - t1[c]) - (t1[c] - t2[c]);
     q.trn = sqrtf(q.d[0] * q.d[0] + q.d[1] * q.d[1] + q.d[2] * q.d[2]);
-}
-
-// the video [start, end) frame f lies in; false when f belongs to none
-DEVINL bool video_of(const int* __restrict__ off, int V, int T, int f, int& start, int& end) {
-    for (int v = 0; v < V; ++v) {
-        if (f >= off[v] && f < off[v + 1]) { start = max(off[v], 0); end = min(off[v + 1], T); return true; }   // (never past the array)
-    }
-    return false;
 }
 
 // out[0] = loss, out[1] = 0.1 * mean(angle), out[2] = mean(trn), out[3] = #triples
@@ -248,26 +208,18 @@ __global__ __launch_bounds__(1024) void root_sm_fwd_kernel(const float* __restri
         if (!video_of(off, V, T, j, start, end) || j + 2 >= end) continue;
         Triple q;
         triple_eval(rtk, stride, j, q);
-        sa += (double)acosf(fminf(fmaxf(q.cosv, kCosLo), kCosHi));
+        sa += (double)angle_of(q.cosv);
         st += (double)q.trn;
         cnt += 1;
     }
-    sa = wave_sum_f64(sa);
-    st = wave_sum_f64(st);
-    cnt = wave_sum_i32(cnt);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh_a[wave] = sa; sh_t[wave] = st; sh_c[wave] = cnt; }
-    __syncthreads();
+    block_sums<16>(sa, st, cnt, sh_a, sh_t, sh_c);
     if (threadIdx.x == 0) {
-        double a = 0.0, t = 0.0;
-        int c = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { a += sh_a[w]; t += sh_t[w]; c += sh_c[w]; }
-        const float rot = (float)(a / (double)c) * 1e-1f;         // no triple: 0 / 0 = NaN, the mean of an empty set
-        const float trn = (float)(t / (double)c);
+        const float rot = (float)(sa / (double)cnt) * 1e-1f;      // no triple: 0 / 0 = NaN, the mean of an empty set
+        const float trn = (float)(st / (double)cnt);
         out[0] = (rot + trn) * 0.1f;
         out[1] = rot;
         out[2] = trn;
-        out[3] = (float)c;
+        out[3] = (float)cnt;
     }
 }
 
@@ -286,7 +238,8 @@ __global__ __launch_bounds__(256) void root_sm_bwd_kernel(const float* __restric
             if (j < start || j + 2 >= end) continue;
             Triple q;
             triple_eval(rtk, stride, j, q);
-            // acos'(c) = -1 / sqrt(1 - c^2) where the cosine is not clamped (torch passes the gradient AT the bounds), times 1/2
+            // acos'(c) = -1 / sqrt(1 - c^2) where the cosine is not clamped (torch passes the gradient AT the bounds), times 1/2;
+            // -ca / sqrt(..) rounds differently from ca * dangle_of(c): this kernel keeps its own form
             const float gc = (q.cosv >= kCosLo && q.cosv <= kCosHi) ? -ca / sqrtf(1.f - q.cosv * q.cosv) * 0.5f : 0.f;
             const float gt = q.trn > 0.f ? ct / q.trn : 0.f;       // torch's norm backward: 0 at norm 0
             const float sgn = r == 1 ? -2.f : 1.f;
@@ -310,10 +263,7 @@ __global__ __launch_bounds__(256) void root_sm_bwd_kernel(const float* __restric
                 }
         }
     }
-    float* p = drtk + (long long)f * stride;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) *reinterpret_cast<float4*>(p + 4 * i) = make_float4(dR[3 * i], dR[3 * i + 1], dR[3 * i + 2], dt[i]);
-    if (stride == 16) *reinterpret_cast<float4*>(p + 12) = make_float4(0.f, 0.f, 0.f, 0.f);
+    store_pose_grad(drtk, stride, f, dR, dt);
 }
 
 // ---- loss assembly -------------------------------------------------------------------------------------------------------
@@ -460,8 +410,7 @@ extern "C" int moda_loss_filter_frame(const float* x, const void* mask, int32_t 
 
 extern "C" int moda_root_sm(const float* rtk, int32_t rows, int64_t T, const int32_t* offsets, int32_t n_videos, float* out4,
                             const float* g, float* drtk, void* stream) {
-    if (!rtk || !offsets || !out4 || (rows != 3 && rows != 4) || T < 1 || T >= (1 << 24) || n_videos < 1) return MODA_EINVAL;
-    if (((uintptr_t)rtk & 15) || ((uintptr_t)drtk & 15)) return MODA_EINVAL;
+    if (!pose_args_ok(rtk, rows, T) || !offsets || !out4 || n_videos < 1 || !al16(drtk)) return MODA_EINVAL;
     const int stride = rows * 4;
     if (g) {
         if (!drtk) return MODA_EINVAL;

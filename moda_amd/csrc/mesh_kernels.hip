@@ -19,10 +19,10 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
 constexpr int kBlock = 256;
 constexpr int kPerThread = 8;
 constexpr int kTile = kBlock * kPerThread;           // MODA_MC_SCAN_TILE
@@ -309,8 +309,6 @@ DEVINL float mc_value(const float* __restrict__ vol, const float* __restrict__ v
 
 DEVINL bool mc_occupied(float v, float thr) { return isfinite(v) && v > thr; }   // :1435 (strict >); not finite: empty
 
-inline unsigned nblocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
-
 // ---- classify ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void mc_classify_kernel(const float* __restrict__ vol, const float* __restrict__ vis,
                                                              int g0, int g1, int g2, float thr, uint8_t* __restrict__ mask,
@@ -367,28 +365,7 @@ struct KeepFace {            // face in the chosen part (its three vertices shar
     DEVINL int operator()(int i) const { return face_ok(faces, i, nv) && label[faces[3LL * i]] == best_root(key) ? 1 : 0; }
 };
 
-// inclusive scan of one value per thread across the block; returns the block total in *total
-DEVINL int block_inclusive_scan(int v, int* lds, int* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
-    if (lane == 63) lds[w] = v;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < kBlock / 64; ++q) {
-        const int s = lds[q];
-        before += q < w ? s : 0;
-        all += s;
-    }
-    __syncthreads();
-    *total = all;
-    return v + before;
-}
-
+// (the scans below are lanes.h's block_scan: the inclusive value of a thread is incl_wave + before)
 template <class F>
 __global__ __launch_bounds__(kBlock) void scan_tile_sum_kernel(F f, int n, int* __restrict__ tile_sum) {
     __shared__ int lds[kBlock / 64];
@@ -397,37 +374,21 @@ __global__ __launch_bounds__(kBlock) void scan_tile_sum_kernel(F f, int n, int* 
 #pragma unroll
     for (int q = 0; q < kPerThread; ++q)
         if (base + q < n) s += f(base + q);
-    int total;
-    block_inclusive_scan(s, lds, &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+    const BlockScan<int> r = block_scan<int, kBlock / 64>(s, lds);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = r.total;
 }
 
 // one block: exclusive scan of the tile sums in 64 bits, total -> *total
 __global__ __launch_bounds__(1024) void scan_tiles_kernel(const int* __restrict__ tile_sum, int nt, int64_t* __restrict__ tile_off,
                                                           int64_t* __restrict__ total) {
     __shared__ long long lds[1024 / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     long long carry = 0;
     for (int b0 = 0; b0 < nt; b0 += 1024) {
         const int b = b0 + (int)threadIdx.x;
-        long long v = b < nt ? (long long)tile_sum[b] : 0;
-        const long long own = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long u = __shfl_up(v, o);
-            if (lane >= o) v += u;
-        }
-        if (lane == 63) lds[w] = v;
-        __syncthreads();
-        long long before = 0, all = 0;
-        for (int q = 0; q < 1024 / 64; ++q) {
-            const long long s = lds[q];
-            before += q < w ? s : 0;
-            all += s;
-        }
-        if (b < nt) tile_off[b] = carry + before + v - own;
-        carry += all;
-        __syncthreads();
+        const long long own = b < nt ? (long long)tile_sum[b] : 0;
+        const BlockScan<long long> r = block_scan<long long, 1024 / 64>(own, lds);
+        if (b < nt) tile_off[b] = carry + r.before + r.incl_wave - own;
+        carry += r.total;
     }
     if (threadIdx.x == 0) *total = carry;
 }
@@ -443,8 +404,8 @@ __global__ __launch_bounds__(kBlock) void scan_tile_kernel(F f, int n, const int
         c[q] = base + q < n ? f(base + q) : 0;
         s += c[q];
     }
-    int total;
-    const int incl = block_inclusive_scan(s, lds, &total);
+    const BlockScan<int> r = block_scan<int, kBlock / 64>(s, lds);
+    const int incl = r.incl_wave + r.before;
     long long run = tile_off[blockIdx.x] + (incl - s);
 #pragma unroll
     for (int q = 0; q < kPerThread; ++q) {
@@ -590,9 +551,7 @@ __global__ __launch_bounds__(kBlock) void uf_label_kernel(int nv, const int* __r
     while (pending) {                                              // wave-uniform: one iteration per distinct root
         const int rl = __shfl(cur, __builtin_ctzll(pending));
         const bool mine = run > 0 && cur == rl;
-        int tot = mine ? run : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+        const int tot = wave_add(mine ? run : 0);
         const unsigned long long same = __ballot(mine);
         if ((threadIdx.x & 63) == __builtin_ctzll(same)) atomicAdd(cnt + rl, tot);
         pending &= ~same;

@@ -2,6 +2,7 @@
 // the bf16 words also train_kernels.hip, loss_kernels.hip): bf16 pack / unpack, the k-slow and k-fast LDS images with their
 // fragment reads (modelled lane by lane in tests/test_gemm3_layout.py), and the parts of the 2 x 2-wave tile engine that
 // gemm_bf16.hip and gemm_x3.hip share -- tile placement, k schedule, the atomic (dW form) epilogue and its host-side planner.
+// Included by those six files only; DEVINL and the alignment test al16 come from lanes.h through moda_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -190,8 +191,6 @@ DEVINL void epi_atomic(f32x16 (&acc)[TR / 64][TC / 64], const float (&xsum8)[8],
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 // The launch plan of the dW form (R x Cn result, K long): 128 x 128 tiles, or 64 x 64 for the 64-wide nets, and the split
 // over k: one workgroup per CU (NG = 2 | 4 wave groups each), every engine with at least two k-tiles of KT
 struct DwPlan { unsigned gr, gc, splits; bool big; };

@@ -1,10 +1,12 @@
-// Device helpers shared by the kernels of libmoda_hip.so (every .hip file of this directory includes it, the bf16 training
-// kernels through mfma_tiles.h): DEVINL, the internal entry points between the files, sincos_rr, quaternion algebra, the DQS
-// point transform, the compositing core, and the layout of the per-set MFMA tables of the fused skin-MLP + warp kernel.
+// Device helpers shared by the rendering and training kernels of libmoda_hip.so (mlp_fused, render, sinkdiv, animate, lossasm
+// and warmup include it directly, the bf16 training kernels, train and loss through mfma_tiles.h; the other files need only
+// lanes.h): the internal entry points between the files, sincos_rr, quaternion algebra, the DQS point transform, the compositing
+// core with its DPP reductions, and the layout of the per-set MFMA tables of the fused skin-MLP + warp kernel.  DEVINL, nblocks,
+// al16, load_id and the shuffle-form wave reductions and scans come from lanes.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#define DEVINL __device__ __forceinline__
+#include "lanes.h"
 
 // gemm_bf16.hip: the bf16-native forms of moda_gemm_f32_ex; true when the call was taken (launch status in *rc)
 struct moda_gemm_desc;

@@ -6,8 +6,8 @@
 //                 reference's xys[:, rndmask].  A frame is cut into tiles of MODA_NVS_SCAN_TILE pixels, one workgroup each; a
 //                 wave takes 256 consecutive pixels of its tile as four ballots of 64.
 //                   1. tile sums     per wave the popcounts of its ballots, the four wave counts summed through LDS;
-//                   2. tile offsets  ONE workgroup walks the tile sums 256 at a time (shuffle scan in a wave, the four wave
-//                                    totals through LDS, a running carry) -> the exclusive offset of every tile, and from the
+//                   2. tile offsets  ONE workgroup walks the tile sums 256 at a time (block_scan: shuffle scan in a wave, the four wave
+//                                    totals through LDS; a running carry) -> the exclusive offset of every tile, and from the
 //                                    first tile of every frame the frame offsets;
 //                   3. tile scans    every tile takes its ballots again; a pixel's slot is its tile's offset + the counts of
 //                                    the waves and ballots before it + the popcount of the lower lanes.
@@ -24,12 +24,11 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-#define DEVINL __device__ __forceinline__
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
@@ -37,8 +36,6 @@ constexpr int kTile = MODA_NVS_SCAN_TILE;
 constexpr int kWaveSpan = kTile / kWaves;          // consecutive pixels of a tile that one wave owns
 constexpr int kPasses = kWaveSpan / 64;            // ballots per wave
 static_assert(kTile % (kWaves * 64) == 0, "a tile is a whole number of ballots per wave");
-
-inline unsigned nblocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 template <bool U8>
 DEVINL bool kept(const void* __restrict__ masks, long long i) {
@@ -83,32 +80,17 @@ __global__ __launch_bounds__(kBlock) void tile_sums_kernel(const void* __restric
 __global__ __launch_bounds__(kBlock) void tile_offsets_kernel(const int* __restrict__ tile_sums, int T, int tpf, int B,
                                                               int* __restrict__ tile_off, int* __restrict__ offsets) {
     __shared__ int s_wave[kWaves];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int carry = 0;
     for (int base = 0; base < T; base += kBlock) {
         const int i = base + (int)threadIdx.x;
         const int v = i < T ? tile_sums[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(incl, o);
-            if (lane >= o) incl += u;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            if (w < wave) before += s_wave[w];
-            total += s_wave[w];
-        }
+        const BlockScan<int> r = block_scan<int, kWaves>(v, s_wave);
         if (i < T) {
-            const int excl = carry + before + incl - v;
+            const int excl = carry + r.before + r.incl_wave - v;
             tile_off[i] = excl;
             if (i % tpf == 0) offsets[i / tpf] = excl;
         }
-        carry += total;
-        __syncthreads();
+        carry += r.total;
     }
     if (threadIdx.x == 0) offsets[B] = carry;
 }

@@ -33,12 +33,11 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-#define DEVINL __device__ __forceinline__
 
 constexpr int kBlock = 256;
 constexpr int kChunk = MODA_CLIP_CHUNK;

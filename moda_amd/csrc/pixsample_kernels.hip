@@ -7,19 +7,15 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
 constexpr int kBlock = 256;
 constexpr int kTile = 1024;               // composite keys of a row staged per pass (8 KiB of LDS)
 constexpr int kShortN = kBlock;           // rows up to this length share a workgroup
-
-DEVINL long long load_id(const void* ids, int is64, long long i) {
-    return is64 ? ((const long long*)ids)[i] : (long long)((const int*)ids)[i];
-}
 
 // The order of moda_topk_rows as one unsigned compare: the high word is the value's key (-0 as +0, every NaN one key above
 // +inf, otherwise the usual monotone map of the IEEE bits), the low word the complemented index, so that a LARGER composite
@@ -220,8 +216,6 @@ __global__ void obs_gather_kernel(const float* __restrict__ imgs, const float* _
     else { src = feats; dst = feat_o; C = 16; c = ch - 8; }
     dst[r * C + c] = (row_ok && col_ok) ? src[(row * C + c) * W + col] : __uint_as_float(0x7fc00000u);
 }
-
-inline unsigned nblocks(long long n, int block) { return (unsigned)((n + block - 1) / block); }
 
 }   // namespace
 

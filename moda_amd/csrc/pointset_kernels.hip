@@ -29,12 +29,12 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
 typedef float f2 __attribute__((ext_vector_type(2)));
 
 constexpr int kBlock = 256;
@@ -45,8 +45,6 @@ constexpr int kGroup = 4;                  // targets per LDS read and per index
 constexpr int kTargetBlocks = 1024;        // four workgroups per CU on 256 CUs
 constexpr int kNSum = MODA_ICP_NSUM;
 constexpr int kIcpMaxBlocks = MODA_ICP_MAX_BLOCKS;
-
-inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 DEVINL f2 dist2_pk(f2 qx, f2 qy, f2 qz, float tx, float ty, float tz) {
     const f2 dx = qx - tx, dy = qy - ty, dz = qz - tz;
@@ -220,9 +218,7 @@ __global__ __launch_bounds__(kBlock) void icp_partial_kernel(const float* __rest
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int q = 0; q < kNSum; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+        const double v = wave_add_down(acc[q]);
         if (lane == 0) lds[w][q] = v;
     }
     __syncthreads();

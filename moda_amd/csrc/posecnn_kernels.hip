@@ -24,19 +24,17 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kBlock = 256;
 constexpr int kKC = MODA_CONV_K_CHUNK;           // channels of one tap per LDS stage
 constexpr int kBigTilesWanted = 256;             // the 64 x 64 form needs one workgroup per CU
-
-inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 struct ConvArgs {
     const float* in;
@@ -215,8 +213,6 @@ __global__ __launch_bounds__(kBlock) void posecnn_tail_kernel(const float* __res
     out[i] = mx;
 }
 
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 }   // namespace
 
 extern "C" int32_t moda_conv2d_tile(int64_t M, int64_t Cout, int32_t tile) {
@@ -238,7 +234,7 @@ extern "C" int moda_conv2d_nhwc(const float* in, const float* w, const float* bi
         return MODA_ESHAPE;
     if (act != MODA_CONV_ACT_NONE && act != MODA_CONV_ACT_RELU && act != MODA_CONV_ACT_LEAKY) return MODA_EINVAL;
     if (tile != MODA_CONV_TILE_AUTO && tile != MODA_CONV_TILE_32 && tile != MODA_CONV_TILE_64) return MODA_EINVAL;
-    if (!in || !w || !bias || !out || !aligned16(in) || !aligned16(w)) return MODA_EINVAL;
+    if (!in || !w || !bias || !out || !al16(in) || !al16(w)) return MODA_EINVAL;
     ConvArgs a;
     a.in = in; a.w = w; a.bias = bias; a.res = res; a.out = out;
     a.M = B * Ho * Wo;
@@ -256,7 +252,7 @@ extern "C" int moda_maxpool3x3s2_nhwc(const float* in, int64_t B, int64_t H, int
     if (B < 1 || H < 1 || W < 1 || C < 1 || C % 4 != 0) return MODA_ESHAPE;
     const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     if ((double)B * H * W * C >= 2147483648.0 * 4 || H > 32768 || W > 32768) return MODA_ESHAPE;
-    if (!in || !out || !aligned16(in) || !aligned16(out)) return MODA_EINVAL;
+    if (!in || !out || !al16(in) || !al16(out)) return MODA_EINVAL;
     const int64_t total = B * Ho * Wo * (C / 4);
     hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(nblocks(total, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, in, total, (int)H, (int)W,
                        (int)(C / 4), (int)Ho, (int)Wo, out);

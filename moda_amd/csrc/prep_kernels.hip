@@ -8,10 +8,10 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
 constexpr int kBlock = 256;
 
 struct Q4 { float w, x, y, z; };
@@ -184,12 +184,6 @@ extern "C" int moda_dq_inverse_bwd(const float* dq, const float* g_out, int64_t 
 // ================================================================================================
 namespace {
 
-DEVINL float wave_sum64(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // raycast (geom_utils.py:746-794): per frame b, pixel s:  v = Kinv_b [x, y, 1],  rays_d = R_b^T v,  rays_o = -R_b^T T_b.
 // One wavefront per frame.  With g_d / g_o given it runs the backward: dR += v g_d^T - T g_o^T, dT = -R sum g_o,
 // dKinv += (R g_d) [x, y, 1]^T, summed over the frame's pixels by wavefront shuffles (no atomics).
@@ -237,9 +231,9 @@ __global__ __launch_bounds__(256) void raycast_kernel(const float* __restrict__ 
     }
     if (bwd) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) { aR[k] = wave_sum64(aR[k]); aK[k] = wave_sum64(aK[k]); }
+        for (int k = 0; k < 9; ++k) { aR[k] = wave_add(aR[k]); aK[k] = wave_add(aK[k]); }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) aT[k] = wave_sum64(aT[k]);
+        for (int k = 0; k < 3; ++k) aT[k] = wave_add(aT[k]);
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 9; ++k) { dR[b * 9 + k] = aR[k]; dK[b * 9 + k] = aK[k]; }

@@ -35,18 +35,15 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
-
 constexpr int kBlock = 256;
 constexpr int kTile = MODA_RASTER_TILE;    // 16 x 16 pixels = one lane per pixel
 constexpr int kList = 2 * kBlock;          // faces waiting in LDS: fewer than kBlock before a step adds at most kBlock
-
-inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // pixel-centre coordinate of column / flipped row index i (:343-346)
 DEVINL double pixel_centre(int i, int S) { return (2.0 * (double)i + 1.0 - (double)S) / (double)S; }

@@ -13,7 +13,7 @@ namespace {
 
 constexpr int kBlock = 256;
 
-static inline int nblocks(long long n, int per = kBlock) { return (int)((n + per - 1) / per); }
+static inline int nblocks(long long n) { return (int)((n + kBlock - 1) / kBlock); }      // (two arguments: the one of lanes.h)
 
 // ------------------------------------------------------------------------------------------------
 // moda_linear_fwd: Y[r,o] = act(b[o] + sum_k W[o, col0+k] X[r,k]) -- 64x64 tile, 4x4 per thread, K step 16

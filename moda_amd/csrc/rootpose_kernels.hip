@@ -13,18 +13,14 @@
 #include <stdint.h>
 
 #include "moda_hip.h"
+#include "lanes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
 constexpr int kBlock = 256;
 constexpr int kIdTile = 1024;
-
-DEVINL long long load_id(const void* ids, int is64, long long i) {
-    return is64 ? ((const long long*)ids)[i] : (long long)((const int*)ids)[i];
-}
 
 DEVINL void mat_mul(const float* A, const float* B, float* C) {          // C = A B
 #pragma unroll
@@ -392,8 +388,6 @@ __global__ void ray_cams_kernel(const float* __restrict__ rtk, const float* __re
     }
     d[12] = dfx; d[13] = dfy; d[14] = dpx; d[15] = dpy;
 }
-
-inline unsigned nblocks(long long n, int block) { return (unsigned)((n + block - 1) / block); }
 
 }   // namespace
 

@@ -12,7 +12,7 @@
 //           DIFFERENCES.  Launched as  INIT (sinkhorn_loop's initialisation at eps_s[0]),  SINKDIV_MAX_STEPS times as STEP (step s
 //           returns at once when s >= n; Jacobi: reads buffer s & 1, writes the averaged potentials into the other) and once as
 //           FINAL (the last extrapolation, no averaging; the softmax-weighted differences of the same pass give the gradient).
-//   reduce  one wavefront: loss = mean(b_x - a_x) + mean(a_y - b_y), lane-strided float64 sums joined by a butterfly.
+//   reduce  one wavefront: loss = mean(b_x - a_x) + mean(a_y - b_y), lane-strided float64 sums joined by wave_add's butterfly.
 // Kernel boundaries order the iterations: no inter-workgroup waiting anywhere.  No float atomics: the same inputs give the same
 // bits on every run.  Device memory is written by plain vector stores.
 #include <hip/hip_runtime.h>
@@ -54,11 +54,8 @@ __global__ __launch_bounds__(256) void sinkdiv_prep_kernel(const float* __restri
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             if (bad) hi[c] = NAN;                                // fmaxf drops a NaN: carry it by hand
-            for (int o = 32; o >= 1; o >>= 1) {
-                lo[c] = fminf(lo[c], __shfl_xor(lo[c], o, 64));
-                const float other = __shfl_xor(hi[c], o, 64);
-                hi[c] = (hi[c] != hi[c] || other != other) ? NAN : fmaxf(hi[c], other);
-            }
+            lo[c] = wave_all(lo[c], [](float a, float b) { return fminf(a, b); });
+            hi[c] = wave_all(hi[c], [](float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); });
         }
         if (lane == 0) {
 #pragma unroll
@@ -230,8 +227,8 @@ __global__ __launch_bounds__(64) void sinkdiv_reduce_kernel(const int* __restric
     double sx = 0.0, sy = 0.0;
     for (int i = threadIdx.x; i < N; i += 64) sx += (double)diff[i];
     for (int j = threadIdx.x; j < M; j += 64) sy += (double)diff[N + j];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { sx += __shfl_xor(sx, o, 64); sy += __shfl_xor(sy, o, 64); }
+    sx = wave_add(sx);
+    sy = wave_add(sy);
     if (threadIdx.x == 0) loss[0] = (float)(sx / (double)N + sy / (double)M);
 }
 

@@ -10,8 +10,6 @@
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
-
 constexpr int BM = 128, BK = 16;
 
 struct GemmArgs {
@@ -1880,8 +1878,7 @@ __global__ __launch_bounds__(256) void fold_final_kernel(const float* __restrict
     if (bd_out != nullptr && threadIdx.x < 64) {          // one wavefront: the bias row (k order within a lane, lanes summed in order)
         float acc = 0.f;
         for (int k = threadIdx.x; k < W; k += 64) acc = fmaf(wrow[k], bf[k], acc);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        acc = wave_add_down(acc);
         if (threadIdx.x == 0) bd_out[o] = bd[o] + acc;
     }
 }

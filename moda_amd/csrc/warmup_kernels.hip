@@ -12,28 +12,19 @@
 //   root smoothness, first order  (:520-537 compute_root_sm_loss)  one workgroup forward; the backward is a gather: one thread per
 //                  frame sums the up to two pairs the frame belongs to, in a fixed order.
 //   matrix -> quaternion  (train_utils.py:664-666, pytorch3d's matrix_to_quaternion restated)  one thread per matrix.
-// No float atomics anywhere: for given inputs every sum has one fixed tree.  Device memory is written by plain vector stores.
+// No float atomics anywhere: for given inputs every sum has one fixed tree (lanes by wave_add's xor butterfly 32..1, waves in index
+// order through LDS; the one-workgroup pose forwards through block_sums of pose_loss.h, which this file shares with
+// lossasm_kernels.hip).  Device memory is written by plain vector stores.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "moda_hip.h"
 #include "moda_dev.h"
+#include "pose_loss.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-DEVINL double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-DEVINL int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- shape initialisation ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void shape_target_kernel(const float* __restrict__ u, long long N, const float* __restrict__ obj_bound,
@@ -78,7 +69,7 @@ __global__ __launch_bounds__(256) void sum_partial_kernel(const float* __restric
             s += (double)a[i];
         }
     }
-    s = wave_sum_f64(s);
+    s = wave_add(s);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) partials[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
@@ -88,7 +79,7 @@ __global__ __launch_bounds__(256) void sum_partial_kernel(const float* __restric
 __global__ __launch_bounds__(1024) void sum_final_kernel(const double* __restrict__ partials, int nb, double div, float* __restrict__ out) {
     __shared__ double sh[16];
     double s = (int)threadIdx.x < nb ? partials[threadIdx.x] : 0.0;
-    s = wave_sum_f64(s);
+    s = wave_add(s);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -108,56 +99,6 @@ __global__ __launch_bounds__(256) void shape_loss_bwd_kernel(const float* __rest
 }
 
 // ---- poses ---------------------------------------------------------------------------------------------------------------
-// torch's clamp(-1 + eps, 1 - eps) on an fp32 tensor: the bounds are formed in double and rounded to fp32 once
-constexpr float kCosLo = (float)(-1.0 + 1e-4), kCosHi = (float)(1.0 - 1e-4);
-
-DEVINL void load_pose(const float* __restrict__ rtk, int stride, long long f, float R[9], float t[3]) {
-    const float* p = rtk + f * stride;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float4 r = *reinterpret_cast<const float4*>(p + 4 * i);       // rows of 4 floats, 16-byte aligned (host-checked)
-        R[3 * i] = r.x; R[3 * i + 1] = r.y; R[3 * i + 2] = r.z; t[i] = r.w;
-    }
-}
-
-// (trace(X Y^T) - 1) / 2: the diagonal entries with their products k = 0, 1, 2 added in that order, then 00 + 11 + 22
-DEVINL float cos_of(const float X[9], const float Y[9]) {
-    float tr = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float c = (X[3 * i] * Y[3 * i] + X[3 * i + 1] * Y[3 * i + 1]) + X[3 * i + 2] * Y[3 * i + 2];
-        tr = i == 0 ? c : tr + c;
-    }
-    return (tr - 1.f) / 2.f;
-}
-
-DEVINL float angle_of(float c) { return acosf(fminf(fmaxf(c, kCosLo), kCosHi)); }
-
-// d acos(clamp(c)) / dc: torch passes the gradient AT the (inclusive) bounds, and nothing outside them
-DEVINL float dangle_of(float c) { return (c >= kCosLo && c <= kCosHi) ? -1.f / sqrtf(1.f - c * c) : 0.f; }
-
-DEVINL void store_pose_grad(float* __restrict__ drtk, int stride, long long f, const float dR[9], const float dt[3]) {
-    float* p = drtk + f * stride;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) *reinterpret_cast<float4*>(p + 4 * i) = make_float4(dR[3 * i], dR[3 * i + 1], dR[3 * i + 2], dt[i]);
-    if (stride == 16) *reinterpret_cast<float4*>(p + 12) = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// both sums of a one-workgroup forward, joined in a fixed tree: lanes by the xor butterfly, waves in index order
-template <int WAVES>
-DEVINL void block_sums(double& a, double& t, int& c, double* sh_a, double* sh_t, int* sh_c) {
-    a = wave_sum_f64(a);
-    t = wave_sum_f64(t);
-    c = wave_sum_i32(c);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh_a[wave] = a; sh_t[wave] = t; sh_c[wave] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = 0.0; t = 0.0; c = 0;
-        for (int w = 0; w < WAVES; ++w) { a += sh_a[w]; t += sh_t[w]; c += sh_c[w]; }
-    }
-}
-
 // out[0] = rot_loss + trn_loss, out[1] = rot_loss = 0.01 * mean(angle), out[2] = trn_loss = mean |tp - tg|^2
 __global__ __launch_bounds__(1024) void rtk_loss_fwd_kernel(const float* __restrict__ rtk, int stride, const float* __restrict__ gt,
                                                             int stride_gt, int T, float* __restrict__ out) {
@@ -204,14 +145,6 @@ __global__ __launch_bounds__(256) void rtk_loss_bwd_kernel(const float* __restri
 #pragma unroll
     for (int c = 0; c < 3; ++c) dt[c] = ct * (tp[c] - tg[c]);
     store_pose_grad(drtk, stride, f, dR, dt);
-}
-
-// the video [start, end) frame f lies in; false when f belongs to none
-DEVINL bool video_of(const int* __restrict__ off, int V, int T, int f, int& start, int& end) {
-    for (int v = 0; v < V; ++v) {
-        if (f >= off[v] && f < off[v + 1]) { start = max(off[v], 0); end = min(off[v + 1], T); return true; }   // (never past the array)
-    }
-    return false;
 }
 
 struct Pair {
@@ -311,10 +244,6 @@ __global__ __launch_bounds__(256) void matrix_to_quat_kernel(const float* __rest
     *reinterpret_cast<float4*>(quat + 4 * i) = make_float4(w * s, x * s, y * s, z * s);
 }
 
-bool pose_args_ok(const float* rtk, int32_t rows, int64_t T) {
-    return rtk && (rows == 3 || rows == 4) && T >= 1 && T < (1 << 24) && !((uintptr_t)rtk & 15);
-}
-
 }  // namespace
 
 extern "C" int moda_shape_target(const float* u, int64_t N, const float* obj_bound, float bound_factor, int32_t ellips, float* pts,
@@ -363,7 +292,7 @@ extern "C" int moda_rtk_loss_fwd(const float* rtk, int32_t rows, const float* rt
 
 extern "C" int moda_rtk_loss_bwd(const float* rtk, int32_t rows, const float* rtk_gt, int32_t rows_gt, int64_t T, const float* g_total,
                                  const float* g_rot, const float* g_trn, float* drtk, void* stream) {
-    if (!pose_args_ok(rtk, rows, T) || !pose_args_ok(rtk_gt, rows_gt, T) || !drtk || ((uintptr_t)drtk & 15)) return MODA_EINVAL;
+    if (!pose_args_ok(rtk, rows, T) || !pose_args_ok(rtk_gt, rows_gt, T) || !drtk || !al16(drtk)) return MODA_EINVAL;
     hipLaunchKernelGGL(rtk_loss_bwd_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rtk, rows * 4, rtk_gt,
                        rows_gt * 4, (int)T, g_total, g_rot, g_trn, drtk);
     return (int)hipGetLastError();
@@ -378,14 +307,14 @@ extern "C" int moda_root_sm1_fwd(const float* rtk, int32_t rows, int64_t T, cons
 
 extern "C" int moda_root_sm1_bwd(const float* rtk, int32_t rows, int64_t T, const int32_t* offsets, int32_t n_videos, const float* out4,
                                  const float* g, float* drtk, void* stream) {
-    if (!pose_args_ok(rtk, rows, T) || !offsets || !out4 || n_videos < 1 || !g || !drtk || ((uintptr_t)drtk & 15)) return MODA_EINVAL;
+    if (!pose_args_ok(rtk, rows, T) || !offsets || !out4 || n_videos < 1 || !g || !drtk || !al16(drtk)) return MODA_EINVAL;
     hipLaunchKernelGGL(root_sm1_bwd_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rtk, rows * 4, (int)T,
                        offsets, (int)n_videos, out4, g, drtk);
     return (int)hipGetLastError();
 }
 
 extern "C" int moda_matrix_to_quat(const float* R, int64_t T, int64_t mat_stride, int64_t row_stride, float* quat, void* stream) {
-    if (!R || !quat || mat_stride < 0 || row_stride < 3 || ((uintptr_t)quat & 15)) return MODA_EINVAL;
+    if (!R || !quat || mat_stride < 0 || row_stride < 3 || !al16(quat)) return MODA_EINVAL;
     if (T < 1 || T >= (1LL << 31)) return MODA_ESHAPE;
     hipLaunchKernelGGL(matrix_to_quat_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, (long long)T,
                        (long long)mat_stride, (long long)row_stride, quat);
