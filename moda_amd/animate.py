@@ -28,13 +28,14 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import abi
 from .feeders import correct_bones, correct_rest_pose
 from .geom_utils import bone_transform, skinning
 from .mesh import _DEFAULT_COLOR, TriMesh, _Visual
 
-FRAME_TILE = 16           # moda_hip.h MODA_ANIM_FRAME_TILE
-BLOCK = 256               # moda_hip.h MODA_ANIM_BLOCK
-MAX_BONES = 64            # moda_hip.h MODA_ANIM_MAX_BONES
+FRAME_TILE = abi.CONSTANTS["MODA_ANIM_FRAME_TILE"]
+BLOCK = abi.CONSTANTS["MODA_ANIM_BLOCK"]
+MAX_BONES = abi.CONSTANTS["MODA_ANIM_MAX_BONES"]
 RINGS, SEGMENTS = 16, 16  # the ellipsoid template's latitude bands and longitude segments
 COLOR_BUDGET_BYTES = 256 << 20     # vertex_colors_frames: the `dir_src` rows of one chunk of frames stay under this
 

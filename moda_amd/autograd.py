@@ -13,6 +13,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib as L
+from . import abi
 
 
 def _f32(t):
@@ -23,9 +24,7 @@ def _dp(t):
     return None if t is None else t.data_ptr()
 
 
-GEMM_BF16 = 1          # moda_hip.h MODA_GEMM_BF16
-GEMM_BF16X3 = 32       # moda_hip.h MODA_GEMM_BF16X3
-GEMM_BF16X6 = 64       # moda_hip.h MODA_GEMM_BF16X6
+GEMM_BF16, GEMM_BF16X3, GEMM_BF16X6 = (abi.CONSTANTS["MODA_GEMM_" + k] for k in ("BF16", "BF16X3", "BF16X6"))
 _TRAIN_PRECISION = os.environ.get("MODA_TRAIN_PRECISION", "fp32")      # exact fp32 unless the environment says otherwise (set_train_precision)
 if _TRAIN_PRECISION not in ("fp32", "bf16", "bf16x3", "bf16x6"):
     raise ValueError(f"MODA_TRAIN_PRECISION={_TRAIN_PRECISION!r}: expected fp32, bf16, bf16x3 or bf16x6")
@@ -37,7 +36,7 @@ TRAIN_BF16_STORE = os.environ.get("MODA_TRAIN_BF16_STORE", "1") != "0"
 # multi-output Functions: let autograd hand None (instead of a freshly zero-filled tensor) for outputs nobody differentiates; every
 # backward here and every kernel behind it takes a null gradient.  MODA_MATERIALIZE_GRADS=1 restores torch's default (an A/B switch)
 MATERIALIZE_GRADS = os.environ.get("MODA_MATERIALIZE_GRADS", "0") == "1"
-_STORE_FLAG = 2
+_STORE_FLAG = abi.CONSTANTS["MODA_TRAIN_BF16_STORE"]
 
 
 def set_train_precision(mode):
@@ -1281,7 +1280,7 @@ class SinkhornDivFn(Function):
         return (gx * g if ctx.needs_input_grad[0] else None), (gy * g if gy is not None else None), None, None, None, None
 
 
-SHAPE_LOSS_MAX_BLOCKS = 1024        # moda_hip.h MODA_SHAPE_LOSS_MAX_BLOCKS
+SHAPE_LOSS_MAX_BLOCKS = abi.CONSTANTS["MODA_SHAPE_LOSS_MAX_BLOCKS"]
 
 
 class ShapeLossFn(Function):

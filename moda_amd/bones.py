@@ -12,10 +12,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import abi
 
-MAX_K = 64                    # MODA_KMEANS_MAX_K
+MAX_K = abi.CONSTANTS["MODA_KMEANS_MAX_K"]
 _BATCH = 16                   # Lloyd iterations enqueued per read-back
-_SCAN_TILE = 2048             # MODA_MC_SCAN_TILE
+_SCAN_TILE = abi.CONSTANTS["MODA_MC_SCAN_TILE"]
 _MASK64 = (1 << 64) - 1
 
 

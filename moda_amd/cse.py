@@ -17,14 +17,15 @@ Deviations from the reference, all deliberate:
 import torch
 
 from . import _lib as L
+from . import abi
 from .geom_utils import K2inv, K2mat, Kmatinv
 
-CHANNELS = 16               # moda_hip.h MODA_CSE_CHANNELS
-QUERY_TILE = 128            # MODA_CSE_QUERY_TILE
-CAND_TILE = 256             # MODA_CSE_CAND_TILE
-OOD_MAX_BLOCKS = 64         # MODA_OOD_MAX_BLOCKS
+CHANNELS = abi.CONSTANTS["MODA_CSE_CHANNELS"]
+QUERY_TILE = abi.CONSTANTS["MODA_CSE_QUERY_TILE"]
+CAND_TILE = abi.CONSTANTS["MODA_CSE_CAND_TILE"]
+OOD_MAX_BLOCKS = abi.CONSTANTS["MODA_OOD_MAX_BLOCKS"]
 OOD_THRESHOLD = 12.0        # ood_check_cse's err_threshold
-_GRID, _DP, _INTERP = 0, 1, 2
+_GRID, _DP, _INTERP = abi.CONSTANTS["MODA_RESAMPLE_GRID"], abi.CONSTANTS["MODA_RESAMPLE_DP"], abi.CONSTANTS["MODA_RESAMPLE_INTERP"]
 
 
 def _no_grad(what, *tensors):
@@ -58,7 +59,7 @@ def _cuda(what, *tensors):
 def argmax_splits(B, N, M, splits=0):
     """(number of candidate ranges, their length) moda_feat_argmax uses; splits = 0: the library's choice."""
     rng = L._I64(0)
-    n = L.load().moda_feat_argmax_splits(int(B), int(N), int(M), int(splits), rng)
+    n = L.load().moda_feat_argmax_splits(int(B), int(N), int(M), int(splits), L._c.byref(rng))
     return int(n), int(rng.value)
 
 

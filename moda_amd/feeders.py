@@ -10,6 +10,7 @@ from torch import nn
 from torch.autograd import Function
 
 from . import _lib as L
+from . import abi
 from . import autograd as A
 from .dual_quat import dq_inverse, dq_mul
 from .geom_utils import bone_transform
@@ -178,7 +179,7 @@ class DQ_RTHead(NeRF):
 
 
 # ---- root (camera) poses: RTHead, RTExplicit, RTExpMLP (nerf.py:307-344, 382-470) on moda_root_pose ----------------------------------
-RAW_NONE, RAW_BASE, RAW_ROWS, RAW_BY_ID = 0, 1, 2, 3          # moda_hip.h MODA_ROOT_RAW_*
+RAW_NONE, RAW_BASE, RAW_ROWS, RAW_BY_ID = (abi.CONSTANTS["MODA_ROOT_RAW_" + k] for k in ("NONE", "BASE", "ROWS", "BY_ID"))
 
 
 def _ids(t):

@@ -19,9 +19,10 @@ OpenCV.  Deviations from the reference, all deliberate:
 import torch
 
 from . import _lib as L
+from . import abi
 from . import cse
 
-INTER_NEAREST, INTER_LINEAR = 0, 1       # moda_hip.h MODA_REMAP_NEAREST / MODA_REMAP_LINEAR (cv2's values)
+INTER_NEAREST, INTER_LINEAR = abi.CONSTANTS["MODA_REMAP_NEAREST"], abi.CONSTANTS["MODA_REMAP_LINEAR"]       # cv2's values
 CROP_FACTOR = 1.2                        # BaseDataset.crop_factor
 MAX_SIDE = 32767                         # frames: pixels a side
 

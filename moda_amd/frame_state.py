@@ -22,11 +22,12 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import abi
 
 ARRAY_KEYS = ('rtk', 'rt_raw', 'idk')
 HOST_KEYS = ('obj_bound', 'mesh_rest')
 _SHAPES = {'rtk': (4, 4), 'rt_raw': (3, 4), 'idk': ()}
-MAX_SPLIT = 256             # moda_hip.h MODA_NEAR_FAR_MAX_SPLIT
+MAX_SPLIT = abi.CONSTANTS["MODA_NEAR_FAR_MAX_SPLIT"]
 SMALL_N = 32                # up to this many points a frame is one lane's loop
 
 

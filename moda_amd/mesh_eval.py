@@ -19,11 +19,12 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import abi
 
 SimilarityTransform = namedtuple("SimilarityTransform", "R T s")
 ICPSolution = namedtuple("ICPSolution", "converged rmse Xt RTs t_history")
 
-_NSUM, _ICP_MAX_BLOCKS = 17, 256           # MODA_ICP_NSUM, MODA_ICP_MAX_BLOCKS
+_NSUM, _ICP_MAX_BLOCKS = abi.CONSTANTS["MODA_ICP_NSUM"], abi.CONSTANTS["MODA_ICP_MAX_BLOCKS"]
 
 
 def _clouds(x, y, what):
@@ -274,7 +275,7 @@ def eval_mesh(verts, verts_gt):
 
 
 # ---- the whole sequence at once: ICP and metrics without read-backs (csrc/icpdev_kernels.hip) -------------------------------
-_NMETRIC = 10                              # MODA_SEQ_NMETRIC
+_NMETRIC = abi.CONSTANTS["MODA_SEQ_NMETRIC"]
 
 
 class ICPSolutionDevice(ICPSolution):

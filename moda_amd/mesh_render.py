@@ -15,8 +15,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
+from . import abi
 
-_REC_DOUBLES, _BOX_INTS = 12, 4            # MODA_RASTER_REC_DOUBLES, MODA_RASTER_BOX_INTS
+_REC_DOUBLES, _BOX_INTS = abi.CONSTANTS["MODA_RASTER_REC_DOUBLES"], abi.CONSTANTS["MODA_RASTER_BOX_INTS"]
 
 
 def _faces_arg(faces, B, what):

@@ -22,14 +22,16 @@ from dataclasses import dataclass
 
 import numpy as np
 
-MLP_BF16 = 1
-MLP_SIGMOID = 2
-MLP_WITH_SIGMA = 4
-MLP_SIGMA_ONLY = 8
-MLP_BF16X3 = 16     # split-bf16: operands as bf16 hi + lo, three MFMAs per product; bf16 fragment geometry, (hi, lo) pairs
-MLP_F16 = 32        # fp16 operands (v_mfma_f32_32x32x16_f16): bf16 fragment geometry and stream layout, fp16 elements
-MLP_F16_HEADS = 64  # with MLP_F16: head fragments as (rounding, residual) pairs -- the dir and rgb layers of the 64-wide network
-                    # (fused skin + warp kernel), the rgb head alone of the 256-wide one (moda_mlp_fwd / _live_fwd)
+from .abi import CONSTANTS as _H
+
+MLP_BF16 = _H["MODA_MLP_BF16"]
+MLP_SIGMOID = _H["MODA_MLP_SIGMOID"]
+MLP_WITH_SIGMA = _H["MODA_MLP_WITH_SIGMA"]
+MLP_SIGMA_ONLY = _H["MODA_MLP_SIGMA_ONLY"]
+MLP_BF16X3 = _H["MODA_MLP_BF16X3"]  # split-bf16: operands as bf16 hi + lo, three MFMAs per product; bf16 fragment geometry, (hi, lo) pairs
+MLP_F16 = _H["MODA_MLP_F16"]        # fp16 operands (v_mfma_f32_32x32x16_f16): bf16 fragment geometry and stream layout, fp16 elements
+MLP_F16_HEADS = _H["MODA_MLP_F16_HEADS"]  # with MLP_F16: head fragments as (rounding, residual) pairs -- the dir and rgb layers of the
+#                                           64-wide network (fused skin + warp kernel), the rgb head alone of the 256-wide one
 
 FRAG_BYTES = 1024
 

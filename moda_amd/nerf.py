@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from . import abi
 from . import mlp_pack as mp
 from . import overflow
 
@@ -584,8 +585,8 @@ class NeRF(nn.Module):
         cr = None if cyc_ref is None else L.dev(cyc_ref).reshape(-1, 3)
         cyc = torch.empty((N, S), device=x.device, dtype=torch.float32) if cr is not None else None
         pt = None if pts_tf is None else L.dev(pts_tf).reshape(-1, 3)
-        desc = L.MlpDesc(W=self.W, D=self.D, n_out=B, flags=flags, n_freq=n_freq, reserved=2 if fold_runs is not None else 0,
-                         overflow=overflow.ptr() if spec.f16 else None)           # 2: MODA_MLP_ROWS_AT_RUNS
+        desc = L.MlpDesc(W=self.W, D=self.D, n_out=B, flags=flags, n_freq=n_freq, reserved=abi.CONSTANTS["MODA_MLP_ROWS_AT_RUNS"] if fold_runs is not None else 0,
+                         overflow=overflow.ptr() if spec.f16 else None)
         win = embedding_window(n_freq, embedding_xyz.alpha)
         for i in range(16):
             desc.window[i] = win[i] if i < n_freq else 0.0

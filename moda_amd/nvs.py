@@ -24,10 +24,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import abi
 from .feeders import chunk_rays, update_delta_rts
 from .geom_utils import K2inv
 
-SCAN_TILE = 1024          # moda_hip.h MODA_NVS_SCAN_TILE
+SCAN_TILE = abi.CONSTANTS["MODA_NVS_SCAN_TILE"]
 MAX_PIXELS = 2 ** 31      # B S S stays below this
 
 NVSFrames = collections.namedtuple("NVSFrames", "rgb depth sil vis rgb8 sil8 vis8 offsets", defaults=(None, None, None, None))

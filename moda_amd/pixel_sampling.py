@@ -17,9 +17,10 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
+from . import abi
 from . import feeders as FD
 
-TOPK_MAX_N = 65536          # moda_hip.h MODA_TOPK_MAX_N
+TOPK_MAX_N = abi.CONSTANTS["MODA_TOPK_MAX_N"]
 _SHORT_N = 256              # rows up to this length share a workgroup; longer rows are one grid row each (at most 65535)
 
 

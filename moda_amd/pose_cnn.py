@@ -23,10 +23,11 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from . import abi
 
-K_CHUNK = 16                # moda_hip.h MODA_CONV_K_CHUNK
-ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2      # MODA_CONV_ACT_*
-TILE_AUTO, TILE_32, TILE_64 = 0, 1, 2        # MODA_CONV_TILE_*
+K_CHUNK = abi.CONSTANTS["MODA_CONV_K_CHUNK"]
+ACT_NONE, ACT_RELU, ACT_LEAKY = (abi.CONSTANTS["MODA_CONV_ACT_" + k] for k in ("NONE", "RELU", "LEAKY"))
+TILE_AUTO, TILE_32, TILE_64 = (abi.CONSTANTS["MODA_CONV_TILE_" + k] for k in ("AUTO", "32", "64"))
 INIT_SEED = 0
 
 

@@ -7,9 +7,10 @@ sinkhorn_divergence.py (tensorized route) and is unpinned: tests hold the kernel
 import torch
 
 from . import autograd as A
+from . import abi
 
-MAX_POINTS = 4096          # include/moda_hip.h MODA_SINKDIV_MAX_POINTS
-BAD_DIAMETER, TOO_MANY_STEPS = 1, 2     # status[0] flags (MODA_SINKDIV_*)
+MAX_POINTS = abi.CONSTANTS["MODA_SINKDIV_MAX_POINTS"]
+BAD_DIAMETER, TOO_MANY_STEPS = abi.CONSTANTS["MODA_SINKDIV_BAD_DIAMETER"], abi.CONSTANTS["MODA_SINKDIV_TOO_MANY_STEPS"]     # status[0] flags
 
 
 def _refuse(option, value, served):

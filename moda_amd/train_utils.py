@@ -9,6 +9,7 @@ parameters; here any non-finite value rejects the step, and `status` = [invalid,
 import torch
 
 from . import _lib as L
+from . import abi
 
 # (aux_out key without its `_g`, factor of opts.clip_scale), in the order of train_utils.py:1285-1306
 GRAD_GROUPS = (
@@ -18,7 +19,7 @@ GRAD_GROUPS = (
     ("skin_aux", .1), ("ks", .1), ("nerf_dp", .1), ("csenet", .1),
 )
 GROUP_INDEX = {name: i for i, (name, _) in enumerate(GRAD_GROUPS)}
-CHUNK = 4096        # MODA_CLIP_CHUNK (include/moda_hip.h)
+CHUNK = abi.CONSTANTS["MODA_CLIP_CHUNK"]
 
 
 def grad_group(name):
