@@ -63,3 +63,6 @@ from .nvs import mask_to_pixels, construct_rays_nvs, render_nvs, crop_short_edge
 from . import animate  # noqa: F401
 from .animate import (skin_weights, displaced_vertices, warp_fw_frames, vertex_colors_frames, bone_ellipsoids,  # noqa: F401
                       skin_colors, export_sequence, MeshSequence, write_obj, read_obj)
+from . import eval_frames as eval_frames_module  # noqa: F401
+from .eval_frames import (nerf_render_eval, render_vid, eval_canvases, flow_to_image, image_grid, to_display,  # noqa: F401
+                          video_frames, eval_frames, EvalFrames)

@@ -68,3 +68,6 @@ def parse(text):
 
 with open(next(h for h in HEADERS if h.endswith("moda_hip.h"))) as _f:
     PROTOTYPES, STRUCTS, CONSTANTS = parse(_f.read())
+# include/moda_hip_vis.h, the evaluation-frame entries: the same shape, tables of its own (the three above are moda_hip.h's alone)
+with open(next(h for h in HEADERS if h.endswith("moda_hip_vis.h"))) as _f:
+    VIS_PROTOTYPES, VIS_STRUCTS, VIS_CONSTANTS = parse(_f.read())
