@@ -66,3 +66,7 @@ from .animate import (skin_weights, displaced_vertices, warp_fw_frames, vertex_c
 from . import eval_frames as eval_frames_module  # noqa: F401
 from .eval_frames import (nerf_render_eval, render_vid, eval_canvases, flow_to_image, image_grid, to_display,  # noqa: F401
                           video_frames, eval_frames, EvalFrames)
+from . import cams  # noqa: F401
+from .cams import (save_cams, fill_invalid_rotations, CamInit, align_sim3, Sim3Fit, eval_root, load_root,  # noqa: F401
+                   visual_hull_align, align_sfm_sim3, draw_cams, draw_cams_pair, render_root_txt)
+from .geom_utils import rtk_invert, rtk_compose, rtk_to_4x4  # noqa: F401

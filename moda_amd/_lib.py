@@ -53,6 +53,8 @@ _SIGNATURES = signatures(abi.PROTOTYPES)
 EXPORTS = tuple(_SIGNATURES)
 _VIS_SIGNATURES = signatures(abi.VIS_PROTOTYPES)          # include/moda_hip_vis.h: the same library, a table of its own
 VIS_EXPORTS = tuple(_VIS_SIGNATURES)
+_CAM_SIGNATURES = signatures(abi.CAM_PROTOTYPES)          # include/moda_hip_cams.h: likewise
+CAM_EXPORTS = tuple(_CAM_SIGNATURES)
 ABI_VERSION = 11       # moda_abi_version() of the library this package was written against (include/moda_hip.h)
 _lib = None
 
@@ -66,7 +68,7 @@ def load():
                 f"{LIB_PATH} is missing: build it with `python -m moda_amd.build` (hipcc, gfx950). "
                 "moda_amd has no CPU or PyTorch fallback.")
         lib = _c.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_VIS_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_VIS_SIGNATURES.items()) + list(_CAM_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.moda_abi_version() != ABI_VERSION:

@@ -71,3 +71,6 @@ with open(next(h for h in HEADERS if h.endswith("moda_hip.h"))) as _f:
 # include/moda_hip_vis.h, the evaluation-frame entries: the same shape, tables of its own (the three above are moda_hip.h's alone)
 with open(next(h for h in HEADERS if h.endswith("moda_hip_vis.h"))) as _f:
     VIS_PROTOTYPES, VIS_STRUCTS, VIS_CONSTANTS = parse(_f.read())
+# include/moda_hip_cams.h, the camera entries (moda_amd/cams.py): a third header of the same shape, tables of its own
+with open(next(h for h in HEADERS if h.endswith("moda_hip_cams.h"))) as _f:
+    CAM_PROTOTYPES, CAM_STRUCTS, CAM_CONSTANTS = parse(_f.read())

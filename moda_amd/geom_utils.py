@@ -331,6 +331,29 @@ def Kmatinv(Kmat):
     return K2inv(mat2K(Kmat)).view(Kmat.shape)
 
 
+def rtk_invert(rtk_in, B):
+    """geom_utils.py:124-153: rtk_in (..., B * 12) = B rigid transforms [rotation 1..9 | translation 1..3] -> their inverses
+    [R^T | -R^T t] in the same layout.  Plain torch on device tensors (not hot)."""
+    rtk = rtk_in.reshape(-1, B, 12)
+    Ri = rtk[..., :9].reshape(-1, B, 3, 3).transpose(-1, -2)
+    ti = -Ri.matmul(rtk[..., 9:12, None])[..., 0]
+    return torch.cat([Ri.reshape(-1, B, 9), ti], -1).reshape(rtk_in.shape)
+
+
+def rtk_to_4x4(rtk):
+    """geom_utils.py:155-168: rtk (bs, 12) = [rotation 1..9 | translation 1..3] -> (bs, 4, 4) with the row 0 0 0 1."""
+    rts = torch.cat([rtk[:, :9].reshape(-1, 3, 3), rtk[:, 9:12, None]], -1)
+    last = torch.zeros((rts.shape[0], 1, 4), device=rtk.device, dtype=rtk.dtype)
+    last[..., 3] = 1
+    return torch.cat([rts, last], 1)
+
+
+def rtk_compose(rtk1, rtk2):
+    """geom_utils.py:170-185: the product rtk1 rtk2 of two sets of rigid transforms (..., 12), in the same layout."""
+    rts = rtk_to_4x4(rtk1.reshape(-1, 12)).matmul(rtk_to_4x4(rtk2.reshape(-1, 12)))
+    return torch.cat([rts[:, :3, :3].reshape(-1, 9), rts[:, :3, 3]], -1).reshape(rtk1.shape)
+
+
 def create_base_se3(bs, device):
     """moda.py:1025-1033: (bs,3,4) identity rotations at t = (0, 0, 0.3)."""
     rt = torch.zeros(bs, 3, 4, device=device)

@@ -14,8 +14,9 @@
 
 The reference's methods read their inputs off the model object; so do the two forward_warmup_* functions here (`model` is the
 DistributedDataParallel-wrapped or bare module).  TRAINING the pose CNN -- warmup_pose with warmup_pose_ep > 0 and no path,
-forward_warmup -- is not implemented (pose_cnn.Encoder refuses training mode), nor is the file and plot side of extract_cams
-(save_cams, align_sfm_sim3, visual_hull_align, process_so3_seq, render_root_txt, draw_cams)."""
+forward_warmup -- is not implemented (pose_cnn.Encoder refuses training mode).  What the reference's extract_cams does after the
+CNN has run -- save_cams, align_sfm_sim3, visual_hull_align, render_root_txt, draw_cams -- is moda_amd/cams.py: hand the tensors
+extract_cams returns to cams.save_cams.  process_so3_seq (pydensecrf) is not implemented."""
 import numpy as np
 import torch
 
@@ -114,9 +115,9 @@ def extract_cams(pose_cnn, dp_feats, frameid, dataid, ks_param, kaug, state, *, 
     receive; None: the CNN's poses, which is what the reference's table holds once save_cams has run (train_utils.py:789).
 
     -> (rtk (N,4,4), is_valid (N,) bool, err_valid (N,) fp32), device tensors; nothing is read back.  The module must be in eval
-    mode (checkpoint.build_pose_cnn returns it so).  A frame's result does not depend on `chunk`.  The file and plot side of the
-    reference's extract_cams (save_cams, align_sfm_sim3, visual_hull_align, process_so3_seq, render_root_txt, draw_cams) is not
-    implemented: the caller reads the returned tensors."""
+    mode (checkpoint.build_pose_cnn returns it so).  A frame's result does not depend on `chunk`.  The reference's
+    extract_cams ends in save_cams: hand the three returned tensors to cams.save_cams (and cams.align_sfm_sim3 where a video has
+    prior cameras; cams.draw_cams draws them).  process_so3_seq (pydensecrf) is not implemented."""
     from types import SimpleNamespace
 
     from .cse import ood_check_cse
