@@ -70,3 +70,5 @@ from . import cams  # noqa: F401
 from .cams import (save_cams, fill_invalid_rotations, CamInit, align_sim3, Sim3Fit, eval_root, load_root,  # noqa: F401
                    visual_hull_align, align_sfm_sim3, draw_cams, draw_cams_pair, render_root_txt)
 from .geom_utils import rtk_invert, rtk_compose, rtk_to_4x4  # noqa: F401
+from . import seq_render  # noqa: F401
+from .seq_render import render_sequence, SeqRender  # noqa: F401

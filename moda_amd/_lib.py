@@ -55,6 +55,8 @@ _VIS_SIGNATURES = signatures(abi.VIS_PROTOTYPES)          # include/moda_hip_vis
 VIS_EXPORTS = tuple(_VIS_SIGNATURES)
 _CAM_SIGNATURES = signatures(abi.CAM_PROTOTYPES)          # include/moda_hip_cams.h: likewise
 CAM_EXPORTS = tuple(_CAM_SIGNATURES)
+_SEQVIS_SIGNATURES = signatures(abi.SEQVIS_PROTOTYPES)    # include/moda_hip_seqvis.h: likewise
+SEQVIS_EXPORTS = tuple(_SEQVIS_SIGNATURES)
 ABI_VERSION = 11       # moda_abi_version() of the library this package was written against (include/moda_hip.h)
 _lib = None
 
@@ -68,7 +70,8 @@ def load():
                 f"{LIB_PATH} is missing: build it with `python -m moda_amd.build` (hipcc, gfx950). "
                 "moda_amd has no CPU or PyTorch fallback.")
         lib = _c.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_VIS_SIGNATURES.items()) + list(_CAM_SIGNATURES.items()):
+        for name, (res, args) in (list(_SIGNATURES.items()) + list(_VIS_SIGNATURES.items()) + list(_CAM_SIGNATURES.items())
+                                  + list(_SEQVIS_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.moda_abi_version() != ABI_VERSION:

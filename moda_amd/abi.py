@@ -74,3 +74,6 @@ with open(next(h for h in HEADERS if h.endswith("moda_hip_vis.h"))) as _f:
 # include/moda_hip_cams.h, the camera entries (moda_amd/cams.py): a third header of the same shape, tables of its own
 with open(next(h for h in HEADERS if h.endswith("moda_hip_cams.h"))) as _f:
     CAM_PROTOTYPES, CAM_STRUCTS, CAM_CONSTANTS = parse(_f.read())
+# include/moda_hip_seqvis.h, the mesh-sequence rendering entries (moda_amd/seq_render.py): a fourth header of the same shape
+with open(next(h for h in HEADERS if h.endswith("moda_hip_seqvis.h"))) as _f:
+    SEQVIS_PROTOTYPES, SEQVIS_STRUCTS, SEQVIS_CONSTANTS = parse(_f.read())

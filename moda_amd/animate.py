@@ -437,6 +437,11 @@ class MeshSequence:
         m.visual = _DeviceVisual(m, self.colors[i] if self.colors.dim() == 3 else self.colors)
         return m
 
+    def render(self, image_hw, **kwargs):
+        """seq_render.render_sequence(self, image_hw, **kwargs): every frame drawn from one of render_vis.py's viewpoints."""
+        from .seq_render import render_sequence
+        return render_sequence(self, image_hw, **kwargs)
+
     def save(self, dir, names, frame_numbers):
         """The reference's file set (extract.py:24-53) under `dir`: mesh-rest.obj, mesh-rest-skin.obj, bone-rest.obj, and per
         frame i <names[i]>-mesh-%05d.obj, <names[i]>-bone-%05d.obj, <names[i]>-cam-%05d.txt (np.savetxt of the 4 x 4) with

@@ -18,10 +18,11 @@ LIB_PATH = os.environ.get("MODA_LIB_PATH") or BUILT_LIB
 # -amdgpu-sched-strategy=max-ilp: the 8 x 256 kernel 12.36 -> 12.11 ms (its default schedule leaves 140 bytes of scratch per
 # lane, this one 20; max-memory-clause 12.13), the other kernels of the file unchanged (A/B on one box, twice).
 FILE_FLAGS = {"mlp_fused.hip": ("-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp")}
-SOURCES = ("mlp_fused.hip", "render_kernels.hip", "train_kernels.hip", "gemm_bf16.hip", "gemm_x3.hip", "bwd64_chain.hip", "bwd256_fused.hip", "loss_kernels.hip", "prep_kernels.hip", "mesh_kernels.hip", "pointset_kernels.hip", "raster_kernels.hip", "bones_kernels.hip", "clip_kernels.hip", "lossasm_kernels.hip", "sinkdiv_kernels.hip", "rootpose_kernels.hip", "optim_kernels.hip", "pixsample_kernels.hip", "frames_kernels.hip", "cse_kernels.hip", "framepair_kernels.hip", "warmup_kernels.hip", "nvs_kernels.hip", "animate_kernels.hip", "posecnn_kernels.hip", "icpdev_kernels.hip", "evalvis_kernels.hip", "cams_kernels.hip")
+SOURCES = ("mlp_fused.hip", "render_kernels.hip", "train_kernels.hip", "gemm_bf16.hip", "gemm_x3.hip", "bwd64_chain.hip", "bwd256_fused.hip", "loss_kernels.hip", "prep_kernels.hip", "mesh_kernels.hip", "pointset_kernels.hip", "raster_kernels.hip", "bones_kernels.hip", "clip_kernels.hip", "lossasm_kernels.hip", "sinkdiv_kernels.hip", "rootpose_kernels.hip", "optim_kernels.hip", "pixsample_kernels.hip", "frames_kernels.hip", "cse_kernels.hip", "framepair_kernels.hip", "warmup_kernels.hip", "nvs_kernels.hip", "animate_kernels.hip", "posecnn_kernels.hip", "icpdev_kernels.hip", "evalvis_kernels.hip", "cams_kernels.hip", "seqvis_kernels.hip")
 HEADERS = (os.path.join(CSRC, "lanes.h"), os.path.join(CSRC, "moda_dev.h"), os.path.join(CSRC, "mfma_tiles.h"),
            os.path.join(CSRC, "pose_loss.h"), os.path.join(ROOT, "include", "moda_hip.h"),
-           os.path.join(ROOT, "include", "moda_hip_vis.h"), os.path.join(ROOT, "include", "moda_hip_cams.h"))
+           os.path.join(ROOT, "include", "moda_hip_vis.h"), os.path.join(ROOT, "include", "moda_hip_cams.h"),
+           os.path.join(ROOT, "include", "moda_hip_seqvis.h"))
 
 
 def _hipcc():
